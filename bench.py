@@ -1,7 +1,14 @@
 """bench.py — device-resident decode throughput of the Vortex canonicalize hot path on MI355X.
 
 Contract:
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  * a plain run does what the headline figure needs and nothing else: it builds C1, warms up,
+    times the K steps, writes the outputs if asked to, and prints the result line.  `--full`
+    adds everything else described below: the other configs (C2-C5, each over >= 20 steps), the
+    CPU baselines, the check of every output, the per-step median pass, the plan report, `--e2e`;
+  * `--dump-outputs DIR` writes what the headline workload's last timed step decoded as
+    DIR/<config>_<array>_<buffer>.npy (float32 / float64, exact; a buffer over its share of
+    48 MiB as a fixed seeded sample).  Inputs are seeded, so two builds can be compared file by file;
   * one process per GPU over RCCL.  Run without torchrun and with N > 1, this script launches
     `python -m torch.distributed.run --nproc-per-node N ... bench.py` as a CHILD before it
     touches a GPU and exits with the child's status; every worker asserts WORLD_SIZE == N;
@@ -573,8 +580,7 @@ def run_workload(wl, steps: int, warmup: int, dist):
     one-kernel step like C1).  No event sits between the timed steps: a timing event between two
     kernels waits for the first one's memory release and stretches each interval by ~2-3 us on a
     60 us kernel (rocprofv3's average of the same launches agrees with the two-event mean, not
-    with per-step events).  A second, untimed pass with an event after every step gives the
-    per-step median."""
+    with per-step events).  The per-step median comes from a pass of its own (step_median)."""
     import torch
     for _ in range(warmup):
         wl.step()
@@ -594,6 +600,17 @@ def run_workload(wl, steps: int, warmup: int, dist):
     elapsed = time.perf_counter() - t0
     wl.ctx.sync()  # surfaces device-side errors (OOB codes, ...)
     kmean = e0.elapsed_time(e1) / steps
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    return elapsed, kmean
+
+
+def step_median(wl, steps: int) -> float:
+    """--full: a second, untimed pass of `steps` steps with an event after every step; the median
+    interval (ms)."""
+    import torch
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     evs[0].record()
     for s in range(steps):
@@ -601,12 +618,51 @@ def run_workload(wl, steps: int, warmup: int, dist):
         evs[s + 1].record()
     torch.cuda.synchronize()
     wl.ctx.sync()
-    kmed = float(np.median([evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]))
-    if dist is not None:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    return elapsed, kmean, kmed
+    return float(np.median([evs[i].elapsed_time(evs[i + 1]) for i in range(steps)]))
+
+
+# ------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET = 48 << 20  # payload bytes of all the .npy files of one run together
+
+
+def _dump_arrays(results):
+    """The canonical outputs of one step as exact numeric host arrays, (name, array) per buffer:
+    primitive values in their own type (64-bit integers as their 32-bit words, so float64 holds
+    them exactly), views as 32-bit words, bits, data and validity as bytes."""
+    import vortex_amd.arrays as A
+    out = []
+    for j, r in enumerate(results):
+        if r.kind == "primitive":
+            v = _host(r.values).view(A.NP_OF_PTYPE[r.ptype])
+            out.append((f"{j}_values", v.view(np.uint32) if v.dtype.kind in "ui" and v.itemsize == 8 else v))
+        elif r.kind == "bool":
+            out.append((f"{j}_values", _host(r.values)))
+        else:
+            out.append((f"{j}_views", _host(r.views).view(np.uint32)))
+            d = _host(r.data)
+            out += [(f"{j}_data{b}", d[o: o + n]) for b, (o, n) in enumerate(r.data_buffers)]
+        if r.validity is not None:
+            out.append((f"{j}_validity", _host(r.validity)))
+    return out
+
+
+def dump_outputs(results, name: str, out_dir: Path) -> dict:
+    """--dump-outputs: write what one step computed as out_dir/<name>_<array>_<buffer>.npy,
+    float32 for bytes and 16-bit values, float64 otherwise.  A buffer with more elements than its
+    share of DUMP_BUDGET is written as a fixed sample: the elements at seeded (the same in every
+    run), sorted positions."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    arrays = _dump_arrays(results)
+    cap = DUMP_BUDGET // (8 * max(1, len(arrays)))
+    written = {}
+    for i, (what, a) in enumerate(arrays):
+        a = a.reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(7 + i).integers(0, a.size, cap))]
+        a = a.astype(np.float32 if a.itemsize <= 2 else np.float64)
+        np.save(out_dir / f"{name}_{what}.npy", a)
+        written[f"{name}_{what}"] = int(a.size)
+    return written
 
 
 def verify_workload(wl, expect) -> dict:
@@ -869,8 +925,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--workloads", default="c1,c2,c3,c4,c5",
-                    help="comma list; c1 is the headline, others go under 'encodings'")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the other workloads (--workloads), the CPU "
+                         "baselines, the check of every output, the per-step median pass, the plan report, --e2e")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the headline workload's last timed step "
+                         "as DIR/<name>.npy (float32/float64; a fixed seeded sample of a large buffer)")
+    ap.add_argument("--workloads", default=None,
+                    help="with --full: comma list (default c1,c2,c3,c4,c5); c1 is the headline, others go under "
+                         "'encodings'.  A plain run measures c1 alone")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true",
@@ -886,6 +949,12 @@ def main():
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="CPU check of the multi-process launch (gloo): print every rank's chunk ranges")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.workloads is not None or args.e2e):
+        ap.error("--workloads and --e2e measure more than the headline figure: add --full")
+    workloads = args.workloads if args.workloads is not None else ("c1,c2,c3,c4,c5" if args.full else "c1")
+    verify = args.full and not args.no_verify
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_workers(args.gpus))
@@ -901,7 +970,7 @@ def main():
 
     # the CPU baseline runs first: its fork pool must not inherit an initialised GPU runtime
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         t0 = time.perf_counter()
         cpu = cpu_baselines(args.cpu_seconds)
         log(f"[bench] cpu baseline: {time.perf_counter() - t0:.1f}s")
@@ -928,7 +997,10 @@ def main():
     if args.copies:
         copies = {k: args.copies for k in copies}
     results = {}
-    for key in [w.strip() for w in args.workloads.split(",") if w.strip()]:
+    keys = [w.strip() for w in workloads.split(",") if w.strip()]
+    dump_key = ("c1" if "c1" in keys else keys[0]) if args.dump_outputs and rank == 0 else None
+    dumped = None
+    for key in keys:
         t0 = time.perf_counter()
         arr, info = makers[key](rng, shard_world, rank, dist) if key == "c5" else makers[key](rng, shard_world, rank)
         if isinstance(arr, tuple) and arr[0] == "file":
@@ -950,9 +1022,13 @@ def main():
         # every config: >= 20 timed steps after >= 3 warm-ups (median of >= 20 reps)
         steps = args.steps if key == "c1" else max(20, args.steps)
         warm = args.warmup if key == "c1" else max(3, args.warmup)
-        elapsed, kmean, kmed = run_workload(wl, steps, warm, dist)
+        elapsed, kmean = run_workload(wl, steps, warm, dist)
+        if key == dump_key:  # the outputs of the copy the last timed step decoded
+            dumped = dump_outputs(wl.results((wl.i - 1) % wl.n_copies), info["name"], Path(args.dump_outputs))
+            log(f"[bench] {info['name']}: outputs written to {args.dump_outputs}")
+        kmed = step_median(wl, steps) if args.full else None
         check = None
-        if not args.no_verify:
+        if verify:
             t1 = time.perf_counter()
             check = verify_workload(wl, info.pop("expect"))
             check["verify_s"] = round(time.perf_counter() - t1, 1)
@@ -969,7 +1045,7 @@ def main():
             t = torch.tensor([float(info["write_bytes"])], dtype=torch.float64, device="cuda")
             dist.all_reduce(t)
             total_write = float(t.item())
-        plan = plan_report(wl, steps) if getattr(wl, "plans", None) else None
+        plan = plan_report(wl, steps) if args.full and getattr(wl, "plans", None) else None
         results[key] = dict(info=info, elapsed=elapsed, ms_per_step=per_step * 1e3, kernel_ms_mean=kmean,
                             kernel_ms_median=kmed, algo_bytes=algo, steps=steps, warmup=warm, plan=plan,
                             value=total_write * steps / elapsed / 1e9, e2e=e2e, check=check, rotation=rotation)
@@ -1008,12 +1084,16 @@ def main():
                          "traffic_source": "profiles/pmc_traffic.json (committed rocprofv3 --pmc FETCH_SIZE / "
                                            "WRITE_SIZE passes of this workload; not this run)",
                          "kernel_ms_mean": round(h["kernel_ms_mean"], 5),
-                         "kernel_ms_median": round(h["kernel_ms_median"], 5),
                          "algorithmic_bytes_per_launch": h["algo_bytes"]},
+            "full": args.full,
             "verified": bool(h["check"] and h["check"]["verified"]),
             "host": {"cpu_model": cpu_model(), "nproc": os.cpu_count(), "cores_used_max": _cpu_cores()},
             "encodings": {},
         }
+        if h["kernel_ms_median"] is not None:
+            line["roofline"]["kernel_ms_median"] = round(h["kernel_ms_median"], 5)
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         for k, r in results.items():
             i = r["info"]
             ent = {
@@ -1023,9 +1103,11 @@ def main():
                 "decoded_GBps_per_gpu": round(r["value"] / world, 2),
                 "decoded_GBps_per_gpu_kernel": round(i["write_bytes"] / (r["kernel_ms_mean"] / 1e3) / 1e9, 1),
                 "hbm_frac_algorithmic": round(r["algo_bytes"] / (r["kernel_ms_mean"] / 1e3) / 1e9 / HBM_PEAK_GBS, 4),
-                "kernel_ms_mean": round(r["kernel_ms_mean"], 5), "kernel_ms_median": round(r["kernel_ms_median"], 5),
+                "kernel_ms_mean": round(r["kernel_ms_mean"], 5),
                 "ms_per_step": round(r["ms_per_step"], 5), "steps": r["steps"], "warmup": r["warmup"],
                 "read_bytes": i["read_bytes"], "write_bytes": i["write_bytes"]}
+            if r["kernel_ms_median"] is not None:
+                ent["kernel_ms_median"] = round(r["kernel_ms_median"], 5)
             if r.get("plan"):
                 ent.update(r["plan"])
             for extra in ("chunks_per_gpu", "chunk_range", "global_chunks", "h2d_region_bytes", "reader_setup_ms"):

@@ -12,7 +12,7 @@ for r in 1 2; do
   for w in 1 2 4 8; do
     for mt in $MT 0; do
       sim=""; [ $w -gt 1 ] && sim="--simulate-world $w"
-      VXG_FUSED_PREPASS_MAX_TILES=$mt timeout -k 10 300 python -u bench.py --workloads c5 $sim --no-cpu-baseline > $O/${TAG}_${w}_$mt.json 2>$O/${TAG}_${w}_$mt.err || exit 4
+      VXG_FUSED_PREPASS_MAX_TILES=$mt timeout -k 10 300 python -u bench.py --full --workloads c5 $sim --no-cpu-baseline > $O/${TAG}_${w}_$mt.json 2>$O/${TAG}_${w}_$mt.err || exit 4
       summ $O/${TAG}_${w}_$mt.json "w=$w maxtiles=$mt"
     done
   done

@@ -4,7 +4,7 @@ Two sources, each a pair of separate rocprofv3 --pmc passes (FETCH_SIZE, WRITE_S
   * per column: `tools/c5_columns.py --mark` (every column decoded alone, a torch kernel before each
     column segments the trace; the column's own JSON line gives its algorithmic bytes = compressed
     buffers read + canonical bytes written);  traffic per step = the column's counter sum / its steps;
-  * the batched 8-GPU shard: `bench.py --workloads c5 --simulate-world 8` (FSST pre-pass, FSST decode,
+  * the batched 8-GPU shard: `bench.py --full --workloads c5 --simulate-world 8` (FSST pre-pass, FSST decode,
     K1g) -- K1g's algorithmic bytes = the shard's minus l_comment's (c5_columns --world 8).
 Correction (MI355X_MICROARCH.md §HBM): bytes = (2 * FETCH_SIZE + WRITE_SIZE) KiB x 1024.
   python tools/c5_traffic.py --cols-fetch D --cols-write D --cols-json F [--shard-fetch D --shard-write D
