@@ -22,7 +22,7 @@ PTYPES = ["u8", "u16", "u32", "u64", "i8", "i16", "i32", "i64", "f16", "f32", "f
 PTYPE = {n: i for i, n in enumerate(PTYPES)}
 DTYPE = dict(NULL=0, BOOL=1, PRIMITIVE=2, UTF8=3, BINARY=4)
 VALIDITY = dict(NON_NULLABLE=0, ALL_VALID=1, ALL_INVALID=2, ARRAY=3)
-ABI_VERSION = 8  # VXG_ABI_VERSION
+ABI_VERSION = 9  # VXG_ABI_VERSION
 STATUS = {0: "OK", 1: "OutOfBounds", 2: "ComputeError", 3: "InvalidArgument", 4: "InvalidSerde",
           5: "NotImplemented", 6: "MismatchedTypes", 7: "AssertionFailed", 8: "HipError",
           9: "OutOfMemory"}
@@ -160,6 +160,16 @@ class VxgLaunchStats(C.Structure):
                 ("k1w_last_bpw_max", C.c_uint32), ("k1w_min_bpw", C.c_uint32), ("k1w_max_bpw", C.c_uint32)]
 
 
+# vxg_cmp_op (compare.rs:13-21 order) and the vxg_compare_scalar flag
+CMP_OP = {"==": 0, "!=": 1, ">": 2, ">=": 3, "<": 4, "<=": 5}
+CMP_NULL_AS_FALSE = 1  # VXG_CMP_NULL_AS_FALSE
+
+
+class VxgCompareInfo(C.Structure):
+    _fields_ = [("fused_launches", C.c_uint32), ("fused_chunks", C.c_uint32), ("fallback_arrays", C.c_uint32),
+                ("patch_launches", C.c_uint32)]
+
+
 class VxgIntStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("min_bits", C.c_uint64), ("max_bits", C.c_uint64), ("trailing_zeros", C.c_uint32),
                 ("reserved", C.c_uint32), ("bit_width_freq", C.c_uint64 * 65)]
@@ -220,6 +230,7 @@ GPU_SIGNATURES = {
     "vxg_bytebool_to_bits": (ST, [VP, VP, U64, VP, U64, VP]),
     "vxg_take_array": (ST, [VP, VP, INT, VP, U64, VP, VP]),
     "vxg_filter_array": (ST, [VP, VP, VP, VP, VP]),
+    "vxg_compare_scalar": (ST, [VP, VP, INT, VP, U32, VP, C.POINTER(VxgCompareInfo), VP]),
     "vxg_fsst_scratch_bytes": (U64, [U64]),
     "vxg_fsst_decode": (ST, [VP, VP, VP, UINT, VP, INT, VP, INT, VP, U64, VP, VP, VP, VP, VP]),
     "vxg_fill": (ST, [VP, UINT, VP, U64, VP, VP]),

@@ -536,6 +536,7 @@ class Canonical:
     validity: Any = None     # torch.uint8 LSB bitmap or None (no nulls)
     data_buffers: Any = None  # [(offset, len)] of each data buffer inside `data`
     binary: bool = False      # VarBinView of DType::Binary (else Utf8)
+    info: Any = None          # compare(): the vxg_compare_info counters (what ran), else None
 
     def to_arrow(self):
         """Canonical::into_arrow (canonical.rs:71-85; varbinview/mod.rs:518 varbinview_as_arrow):
@@ -724,6 +725,58 @@ def filter(a: Array, predicate: Array, ctx: Context) -> Canonical:
         res.validity = vt[: (k + 7) // 8]
     ctx.sync()
     return res
+
+
+def compare(a: Array, op: str, scalar, ctx: Context, null_as_false: bool = False, sync: bool = True,
+            out_values=None, out_validity=None) -> Canonical:
+    """compute::compare with a scalar (vortex-array/src/compute/compare.rs:81-124) on the GPU
+    (vxg_compare_scalar): a Bool canonical whose bit i is `value i <op> scalar`, op one of
+    "==", "!=", ">", ">=", "<", "<=" -- integers in the ptype's signedness, floats as IEEE; value
+    bits of null rows are 0.  BitPacked / FoR / ZigZag / ALP cascades (and chunks of those) are
+    compared in the packed domain; `res.info` says what ran.  Both bitmaps hold
+    ((len + 63) // 64) * 8 bytes; `out_values` / `out_validity` (device uint8 tensors of that size,
+    8-byte aligned) are written in place.  null_as_false: no validity, values = compare AND valid
+    (RowFilter's null_as_false): `predicate_from(res)` is then a filter predicate."""
+    import torch
+    if op not in _lib.CMP_OP:
+        raise VortexError(3, f"compare: unknown operator {op!r}")
+    keep: list = []
+    node = flatten(a, keep)
+    dev = torch.device("cuda", ctx.device)
+    nbytes = ((a.len + 63) // 64) * 8
+    vals = out_values if out_values is not None else torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    out = _lib.VxgCanonical()
+    out.values = vals.data_ptr()
+    vt = None
+    if a.nullable and not null_as_false:
+        vt = out_validity if out_validity is not None else torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        out.validity = vt.data_ptr()
+    sc = np.array([scalar]).astype(NP_OF_PTYPE[a.ptype]).tobytes() if a.dtype == DTYPE["PRIMITIVE"] else bytes(8)
+    sbuf = (C.c_uint8 * 8)(*sc.ljust(8, b"\0")[:8])
+    info = _lib.VxgCompareInfo()
+    flags = _lib.CMP_NULL_AS_FALSE if null_as_false else 0
+    _lib.check(ctx.lib.vxg_compare_scalar(ctx.handle, C.byref(node), _lib.CMP_OP[op], sbuf, flags, C.byref(out),
+                                          C.byref(info), ctx.stream_ptr()))
+    res = Canonical("bool", a.len, a.ptype, values=vals[:nbytes],
+                    info={f: int(getattr(info, f)) for f, _ in info._fields_})
+    if out.validity:
+        if vt is None or out.validity != vt.data_ptr():
+            raise VortexError(7, "engine allocated validity for a non-nullable dtype")
+        res.validity = vt[:nbytes]
+    if sync:
+        ctx.sync()
+    return res
+
+
+def predicate_from(mask: Canonical) -> Array:
+    """A non-nullable Bool Array over the device bitmap of a Bool canonical (no host round trip):
+    `filter(a, predicate_from(compare(a, "<", s, ctx, null_as_false=True)), ctx)`."""
+    if mask.kind != "bool":
+        _bail("MismatchedTypes", "predicate_from needs a Bool canonical")
+    if mask.validity is not None:
+        _bail("InvalidArgument", "predicate must be non-nullable bool: compare with null_as_false=True")
+    return Array(ENC["BOOL"], mask.len, DTYPE["BOOL"], "u8", False, VALIDITY["NON_NULLABLE"],
+                 {"first_byte_bit_offset": 0}, [mask.values])
 
 
 def _kind_of_node(node: _lib.VxgArray) -> str:

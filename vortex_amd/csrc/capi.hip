@@ -19,6 +19,7 @@
 #include <tuple>
 #include <vector>
 
+#include "compare.hpp"
 #include "encode_gpu.hpp"
 #include "filter.hpp"
 #include "k1g.hpp"
@@ -34,6 +35,7 @@ static_assert(sizeof(vxg::ChunkTable) <= 4096, "ChunkTable exceeds the kernarg l
 static_assert(sizeof(vxg::FsstTable) <= 4096, "FsstTable exceeds the kernarg limit");
 static_assert(sizeof(vxg::RunEndTable) <= 4096, "RunEndTable exceeds the kernarg limit");
 static_assert(sizeof(vxg::VarBinTable) <= 4096, "VarBinTable exceeds the kernarg limit");
+static_assert(sizeof(vxg::CmpTable) + 32 <= 4096, "CmpTable and the compare arguments exceed the kernarg limit");
 
 namespace vxg {
 
@@ -537,6 +539,9 @@ class Planner {
     vxg_status take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out);
     // compute::filter (filter.hip): the rows whose predicate bit is set + validity.filter
     vxg_status filter(const vxg_array& a, const vxg_array& pred, vxg_canonical& out);
+    // compute::compare with a scalar (compare.hip): a Bool canonical, bit i = op(value i, scalar)
+    vxg_status compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
+                       vxg_compare_info& info);
     vxg_status canonical_size(const vxg_array& a, uint64_t& vb, uint64_t& db);
     // Data buffers of a string canonical, placed 16-byte aligned in one allocation.
     vxg_status string_layout(const vxg_array& a, std::vector<vxg_data_buffer>& bufs, uint64_t& extent);
@@ -620,6 +625,19 @@ class Planner {
 
     vxg_status take_values(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, void* dst);
     vxg_status take_patches(const vxg_array& sp, TakePatches& p);
+    // A BitPacked-rooted cascade the fused compare kernel serves, validated (compare).
+    struct CmpFused {
+        const vxg_array* arr;    // the array or chunk
+        const vxg_array* bp;     // its BitPacked leaf
+        const vxg_array* outer;  // ALP patches, or null
+        int T, ck;
+        Epi epi;
+        EpiParams ep;
+        CmpChunk d;
+        bool excl;
+    };
+    vxg_status compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused);
+    vxg_status launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op);
     vxg_status validity_into(const vxg_array& a, void** bitmap);
     // OR the values of a Bool-dtype array into the zeroed bit buffer `bits` at bit `off`.
     vxg_status bools_into(const vxg_array& a, void* bits, uint64_t off);
@@ -1378,6 +1396,251 @@ vxg_status Planner::take(const vxg_array& a, const void* idx, int iw, bool isg, 
     if (!out.validity) VXG_TRY(hip_check(hipMalloc(&out.validity, bytes ? bytes : 4), "take validity alloc"));
     return launch_gather_bits(out.validity, idx, iw, isg, n, static_cast<const uint8_t*>(src), a.len, ctx_->c.err_word,
                               s_);
+}
+
+// ---- compute::compare with a scalar (vortex-array/src/compute/compare.rs:81-124) ----------
+// Is `a` a cascade the fused kernel serves -- BitPacked, FoR(BitPacked), ZigZag or ALP over
+// either?  Then validate its packed buffer exactly like take_values and describe it.
+vxg_status Planner::compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused) {
+    *fused = false;
+    f = CmpFused{};
+    f.arr = &a;
+    f.epi = Epi::Plain;
+    f.ck = ptype_is_signed(a.ptype) ? kCmpSigned : kCmpUnsigned;
+    auto fl_child = [&](const vxg_array* c) -> const vxg_array* {  // FoR(BitPacked) or BitPacked
+        if (c && c->encoding == VXG_ENC_FL_FOR && child(*c, 0) && child(*c, 0)->encoding == VXG_ENC_FL_BITPACKED) {
+            f.ep.reference = c->meta.for_.reference;
+            f.ep.shift = c->meta.for_.shift;
+            return child(*c, 0);
+        }
+        return c && c->encoding == VXG_ENC_FL_BITPACKED ? c : nullptr;
+    };
+    switch (a.encoding) {
+    case VXG_ENC_FL_BITPACKED: f.bp = &a; break;
+    case VXG_ENC_FL_FOR:
+        f.bp = fl_child(&a);
+        f.epi = Epi::For;
+        break;
+    case VXG_ENC_ZIGZAG:
+        if (!ptype_is_signed(a.ptype)) return VXG_OK;  // the fallback reports it
+        f.bp = fl_child(child(a, 0));
+        f.epi = Epi::ForZigZag;
+        break;
+    case VXG_ENC_ALP: {
+        const bool f32 = a.ptype == VXG_F32;
+        const unsigned e = a.meta.alp.e, fx = a.meta.alp.f;
+        if ((f32 && (e > 10 || fx > 10)) || (!f32 && (a.ptype != VXG_F64 || e > 23 || fx > 23))) return VXG_OK;
+        f.bp = fl_child(child(a, 0));
+        f.epi = f32 ? Epi::AlpF32 : Epi::AlpF64;
+        f.ck = kCmpFloat;
+        f.ep.alp_a = f32 ? double(kF10f[fx]) : kF10d[fx];
+        f.ep.alp_b = f32 ? double(kIF10f[e]) : kIF10d[e];
+        if (f.bp && a.meta.alp.has_patches) {
+            if (!child(a, 1)) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: patches child missing");
+            f.outer = child(a, 1);
+        }
+        break;
+    }
+    default: return VXG_OK;
+    }
+    if (!f.bp || !ptype_is_int(f.bp->ptype) || !(ptype_is_int(a.ptype) || f.ck == kCmpFloat)) return VXG_OK;
+    f.T = 8 * width(*f.bp);
+    if (f.T != 8 * width(a) || f.bp->len != a.len) return VXG_OK;
+    const vxg_buffer* pb = buf(*f.bp, 0);
+    const unsigned W = f.bp->meta.bitpacked.bit_width, off = f.bp->meta.bitpacked.offset;
+    if (off > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
+    if (W > unsigned(f.T)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
+    const uint64_t nblk = (a.len + off + 1023) / 1024, have = pb ? pb->len : 0;
+    if (W > 0 && have != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
+                                                       " packed bytes, got " + std::to_string(have));
+    if (W > 0 && (reinterpret_cast<uintptr_t>(pb->ptr) & 15))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "packed buffer must be 16-byte aligned");
+    if (a.len > kCmpMaxLen) return set_error(VXG_ERR_INVALID_ARGUMENT, "array too long for one compare launch");
+    // patch children are checked here, before the caller allocates or launches anything
+    auto patch_values = [&](const vxg_array& sp) -> const vxg_array* {
+        return sp.encoding == VXG_ENC_SPARSE && child(sp, 0) && child(sp, 1) ? child(sp, 1) : nullptr;
+    };
+    if (f.bp->meta.bitpacked.has_patches) {
+        if (!child(*f.bp, 0)) return set_error(VXG_ERR_INVALID_ARGUMENT, "BitPacked patches child missing");
+        const vxg_array* pv = patch_values(*child(*f.bp, 0));
+        if (pv && width(*pv) != f.T / 8)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "BitPacked patch values must have the array's width");
+    }
+    if (f.outer) {
+        const vxg_array* pv = patch_values(*f.outer);
+        if (pv && pv->ptype != a.ptype)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "ALP patch values must have the array's ptype");
+    }
+    f.ep.err = ctx_->c.err_word;
+    f.d.packed = pb ? static_cast<const uint8_t*>(pb->ptr) : nullptr;
+    f.d.len_lo = uint32_t(a.len);
+    f.d.len_hi = uint8_t(a.len >> 32);
+    f.d.out_bit = out_bit;
+    f.d.reference = f.ep.reference;
+    f.d.alp_e = a.encoding == VXG_ENC_ALP ? a.meta.alp.e : 0;
+    f.d.alp_f = a.encoding == VXG_ENC_ALP ? a.meta.alp.f : 0;
+    f.d.offset = uint16_t(off);
+    f.d.shift = uint8_t(f.ep.shift);
+    f.d.W = uint8_t(W);
+    *fused = true;
+    return VXG_OK;
+}
+
+// The chunks of one kernel instantiation (T, epilogue, compared type; at most kCmpArgChunks) in one
+// launch: the table is the kernel argument -- nothing is uploaded and no host state outlives the call.
+vxg_status Planner::launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op) {
+    uint64_t blocks = 0;
+    for (const CmpFused* f : group) blocks += f->d.n_blocks();
+    // small launches take fewer blocks per workgroup (>= 4: one per wave), like K1w's rule
+    uint32_t pick = uint32_t(std::min<uint64_t>(32, blocks / 1024)) & ~3u;
+    if (pick < 4) pick = 4;
+    CmpTable tab{};
+    uint64_t groups = 0;
+    uint32_t lds = 0;
+    for (const CmpFused* f : group) {
+        CmpChunk& c = tab.c[tab.n++];
+        c = f->d;
+        const uint32_t bpw = std::min(cmp_bpw_max(c.W), pick);
+        c.bpw_excl = uint8_t(bpw | (f->excl ? 0x80u : 0u));
+        c.first_group = uint32_t(groups);
+        groups += (c.n_blocks() + bpw - 1) / bpw;
+        lds = std::max(lds, bpw * 128u * c.W);
+    }
+    if (groups == 0) groups = 1;  // an empty array: one workgroup that finds no block
+    const CmpFused& f0 = *group[0];
+    // (+ one word row of slack: a value's second word is read unconditionally)
+    return launch_cmp_packed(f0.T, f0.epi, f0.ck, tab, groups, lds + 128, out, scalar_bits, op, s_);
+}
+
+vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
+                            vxg_compare_info& info) {
+    if (a.dtype != VXG_DTYPE_PRIMITIVE) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare supports primitive arrays");
+    if (width(a) == 0 || a.ptype == VXG_F16) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare does not support f16");
+    if (op < VXG_CMP_EQ || op > VXG_CMP_LTE)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare operator " + std::to_string(op));
+    if (flags & ~uint32_t(VXG_CMP_NULL_AS_FALSE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare flags");
+    const uint64_t n = a.len, words = (n + 63) / 64, bytes = words * 8;
+
+    // the pieces: the array itself, or the chunks of a top-level ChunkedArray at their bit offsets
+    std::vector<std::pair<const vxg_array*, uint64_t>> pieces;
+    if (a.encoding == VXG_ENC_CHUNKED) {
+        if (a.n_children != a.meta.chunked.nchunks + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked child count != nchunks + 1");
+        uint64_t off = 0;
+        for (uint32_t i = 1; i < a.n_children; i++) {
+            const vxg_array& c = a.children[i];
+            if (c.dtype != a.dtype || c.ptype != a.ptype)
+                return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the same dtype");
+            pieces.emplace_back(&c, off);
+            off += c.len;
+        }
+        if (off != n) return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked chunk lengths do not sum to len");
+    } else {
+        pieces.emplace_back(&a, 0);
+    }
+    // classify and validate every piece before anything is allocated or launched
+    std::vector<CmpFused> fused;
+    std::vector<std::pair<const vxg_array*, uint64_t>> plain;
+    fused.reserve(pieces.size());
+    bool zero = false;  // some word is ORed in: the bitmap starts zeroed
+    auto word_edges = [&](uint64_t ob, uint64_t len) { return ob % 64 == 0 && ((ob + len) % 64 == 0 || ob + len == n); };
+    for (const auto& [p, ob] : pieces) {
+        CmpFused f;
+        bool is_fused;
+        VXG_TRY(compare_shape(*p, ob, f, &is_fused));
+        if (is_fused) {
+            f.excl = word_edges(ob, p->len) && f.d.offset % 64 == 0;
+            if (p->len == 0 && p != &a) {  // an empty chunk: counted, nothing to launch
+                info.fused_chunks++;
+                continue;
+            }
+            zero = zero || (p->len && !f.excl);
+            fused.push_back(f);
+        } else {
+            zero = zero || (p->len && !word_edges(ob, p->len));
+            plain.emplace_back(p, ob);
+        }
+    }
+
+    out.kind = VXG_ENC_BOOL;
+    out.len = n;
+    out.dtype = VXG_DTYPE_BOOL;
+    out.ptype = VXG_U8;
+    out.values_bytes = bytes;
+    if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, bytes ? bytes : 8), "compare values alloc"));
+    if (reinterpret_cast<uintptr_t>(out.values) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare output must be 8-byte aligned");
+    if (zero) VXG_TRY(launch_copy_bytes(out.values, nullptr, bytes, s_));
+
+    // fused launches, one per kernel instantiation
+    std::vector<CmpFused*> order;
+    for (CmpFused& f : fused) order.push_back(&f);
+    std::stable_sort(order.begin(), order.end(), [](const CmpFused* x, const CmpFused* y) {
+        return std::make_tuple(x->T, int(x->epi), x->ck) < std::make_tuple(y->T, int(y->epi), y->ck);
+    });
+    for (size_t i = 0; i < order.size();) {
+        size_t j = i;
+        while (j < order.size() && j - i < size_t(kCmpArgChunks) && order[j]->T == order[i]->T &&
+               order[j]->epi == order[i]->epi && order[j]->ck == order[i]->ck)
+            j++;
+        std::vector<CmpFused*> group(order.begin() + i, order.begin() + j);
+        VXG_TRY(launch_compare_group(group, out.values, scalar_bits, op));
+        info.fused_launches++;
+        info.fused_chunks += uint32_t(j - i);
+        i = j;
+    }
+    // patched rows are compared again: BitPacked's raw values through the epilogue, then ALP's
+    for (const CmpFused& f : fused) {
+        if (f.bp->meta.bitpacked.has_patches) {
+            TakePatches tp;
+            VXG_TRY(take_patches(*child(*f.bp, 0), tp));
+            VXG_TRY(launch_cmp_patch(f.T, f.epi, f.ck, tp, f.d.len(), out.values, f.d.out_bit, f.ep, scalar_bits, op, s_));
+            info.patch_launches += tp.n != 0;
+        }
+        if (f.outer) {
+            TakePatches tp;
+            VXG_TRY(take_patches(*f.outer, tp));
+            VXG_TRY(launch_cmp_patch_raw(a.ptype, tp, f.d.len(), out.values, f.d.out_bit, scalar_bits, op, ctx_->c.err_word,
+                                         s_));
+            info.patch_launches += tp.n != 0;
+        }
+    }
+    // every other encoding: the canonical values (a Primitive array in place), then the plain kernel
+    for (const auto& [p, ob] : plain) {
+        const void* pv;
+        VXG_TRY(view_primitive(*p, &pv));
+        if (reinterpret_cast<uintptr_t>(pv) % uint64_t(width(a)))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "primitive buffer must be aligned to the value width");
+        VXG_TRY(launch_cmp_plain(a.ptype, pv, p->len, out.values, ob, scalar_bits, op, word_edges(ob, p->len), s_));
+        info.fallback_arrays++;
+    }
+
+    // value bits of null rows are 0; null_as_false drops the validity (filtering.rs:42)
+    const vxg_array* vnode;
+    int vkind;
+    VXG_TRY(validity_source(a, &vnode, &vkind));
+    const bool null_as_false = (flags & VXG_CMP_NULL_AS_FALSE) != 0;
+    if (vkind == 0) {
+        out.validity = nullptr;
+        return VXG_OK;
+    }
+    void* vbits = nullptr;
+    if (null_as_false) VXG_TRY(temp(bytes, &vbits));
+    else if (out.validity) vbits = out.validity;
+    else {
+        VXG_TRY(hip_check(hipMalloc(&vbits, bytes ? bytes : 8), "compare validity alloc"));
+        out.validity = vbits;  // (the entry point releases it if a later step fails)
+    }
+    if (reinterpret_cast<uintptr_t>(vbits) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare validity must be 8-byte aligned");
+    if (n) {  // (an empty array's bitmaps hold no bytes: nothing is written)
+        VXG_TRY(launch_copy_bytes(vbits, nullptr, bytes, s_));
+        VXG_TRY(validity_into(a, &vbits));
+        VXG_TRY(launch_and_words(out.values, vbits, words, s_));
+    }
+    out.validity = null_as_false ? nullptr : vbits;
+    return VXG_OK;
 }
 
 // compute::filter (compute/filter.rs:23-52).  The predicate (any Bool encoding) becomes a bit
@@ -2803,6 +3066,27 @@ vxg_status vxg_take_array(vxg_ctx* ctx, const vxg_array* a, int indices_ptype, c
     if (!ptype_is_int(indices_ptype)) return set_error(VXG_ERR_INVALID_ARGUMENT, "take indices must be integers");
     Planner p(ctx, S(stream));
     return p.take(*a, indices, ptype_width(indices_ptype), ptype_is_signed(indices_ptype), n_indices, *out);
+}
+
+vxg_status vxg_compare_scalar(vxg_ctx* ctx, const vxg_array* a, int op, const void* scalar_host, uint32_t flags,
+                              vxg_canonical* out, vxg_compare_info* info, void* stream) {
+    VXG_TRY(use_device(ctx));
+    if (!a || !out || !scalar_host) return set_error(VXG_ERR_INVALID_ARGUMENT, "null array/scalar/out");
+    uint64_t bits = 0;  // the scalar's little-endian bytes (a->ptype's width; checked by the planner)
+    if (a->dtype == VXG_DTYPE_PRIMITIVE) std::memcpy(&bits, scalar_host, size_t(ptype_width(a->ptype)));
+    vxg_compare_info ci{};
+    Planner p(ctx, S(stream));
+    void* const values_in = out->values;
+    void* const validity_in = out->validity;
+    const vxg_status st = p.compare(*a, op, bits, flags, *out, ci);
+    if (info) *info = ci;
+    if (st != VXG_OK) {  // nothing engine-allocated is handed back with an error
+        if (out->values && out->values != values_in) (void)hipFree(out->values);
+        if (out->validity && out->validity != validity_in) (void)hipFree(out->validity);
+        out->values = values_in;
+        out->validity = validity_in;
+    }
+    return st;
 }
 
 // ---- encoders on the GPU (encode_gpu.hip, fl_pack_impl.hpp) ----------------------------
