@@ -22,7 +22,7 @@ PTYPES = ["u8", "u16", "u32", "u64", "i8", "i16", "i32", "i64", "f16", "f32", "f
 PTYPE = {n: i for i, n in enumerate(PTYPES)}
 DTYPE = dict(NULL=0, BOOL=1, PRIMITIVE=2, UTF8=3, BINARY=4)
 VALIDITY = dict(NON_NULLABLE=0, ALL_VALID=1, ALL_INVALID=2, ARRAY=3)
-ABI_VERSION = 9  # VXG_ABI_VERSION
+ABI_VERSION = 10  # VXG_ABI_VERSION
 STATUS = {0: "OK", 1: "OutOfBounds", 2: "ComputeError", 3: "InvalidArgument", 4: "InvalidSerde",
           5: "NotImplemented", 6: "MismatchedTypes", 7: "AssertionFailed", 8: "HipError",
           9: "OutOfMemory"}
@@ -170,6 +170,11 @@ class VxgCompareInfo(C.Structure):
                 ("patch_launches", C.c_uint32)]
 
 
+class VxgCompareBytesInfo(C.Structure):
+    _fields_ = [("dict_launches", C.c_uint32), ("dict_chunks", C.c_uint32), ("table_launches", C.c_uint32),
+                ("direct_launches", C.c_uint32), ("direct_chunks", C.c_uint32), ("fallback_arrays", C.c_uint32)]
+
+
 class VxgIntStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("min_bits", C.c_uint64), ("max_bits", C.c_uint64), ("trailing_zeros", C.c_uint32),
                 ("reserved", C.c_uint32), ("bit_width_freq", C.c_uint64 * 65)]
@@ -231,6 +236,7 @@ GPU_SIGNATURES = {
     "vxg_take_array": (ST, [VP, VP, INT, VP, U64, VP, VP]),
     "vxg_filter_array": (ST, [VP, VP, VP, VP, VP]),
     "vxg_compare_scalar": (ST, [VP, VP, INT, VP, U32, VP, C.POINTER(VxgCompareInfo), VP]),
+    "vxg_compare_bytes": (ST, [VP, VP, INT, VP, U64, U32, VP, C.POINTER(VxgCompareBytesInfo), VP]),
     "vxg_fsst_scratch_bytes": (U64, [U64]),
     "vxg_fsst_decode": (ST, [VP, VP, VP, UINT, VP, INT, VP, INT, VP, U64, VP, VP, VP, VP, VP]),
     "vxg_fill": (ST, [VP, UINT, VP, U64, VP, VP]),

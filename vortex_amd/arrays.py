@@ -736,7 +736,10 @@ def compare(a: Array, op: str, scalar, ctx: Context, null_as_false: bool = False
     compared in the packed domain; `res.info` says what ran.  Both bitmaps hold
     ((len + 63) // 64) * 8 bytes; `out_values` / `out_validity` (device uint8 tensors of that size,
     8-byte aligned) are written in place.  null_as_false: no validity, values = compare AND valid
-    (RowFilter's null_as_false): `predicate_from(res)` is then a filter predicate."""
+    (RowFilter's null_as_false): `predicate_from(res)` is then a filter predicate.
+    A utf8/binary array takes `scalar` as bytes or str (UTF-8) and goes to vxg_compare_bytes: bytes
+    compared unsigned and lexicographically; Dict, VarBin, VarBinView and FSST are compared where
+    they lie and `res.info` holds vxg_compare_bytes_info's counters."""
     import torch
     if op not in _lib.CMP_OP:
         raise VortexError(3, f"compare: unknown operator {op!r}")
@@ -751,12 +754,20 @@ def compare(a: Array, op: str, scalar, ctx: Context, null_as_false: bool = False
     if a.nullable and not null_as_false:
         vt = out_validity if out_validity is not None else torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
         out.validity = vt.data_ptr()
-    sc = np.array([scalar]).astype(NP_OF_PTYPE[a.ptype]).tobytes() if a.dtype == DTYPE["PRIMITIVE"] else bytes(8)
-    sbuf = (C.c_uint8 * 8)(*sc.ljust(8, b"\0")[:8])
-    info = _lib.VxgCompareInfo()
     flags = _lib.CMP_NULL_AS_FALSE if null_as_false else 0
-    _lib.check(ctx.lib.vxg_compare_scalar(ctx.handle, C.byref(node), _lib.CMP_OP[op], sbuf, flags, C.byref(out),
-                                          C.byref(info), ctx.stream_ptr()))
+    if a.dtype in (DTYPE["UTF8"], DTYPE["BINARY"]) and isinstance(scalar, (bytes, bytearray, memoryview, str)):
+        # strings (vxg_compare_bytes): the scalar's bytes, a str as UTF-8
+        sc = scalar.encode("utf-8") if isinstance(scalar, str) else bytes(scalar)
+        sbuf = (C.c_uint8 * max(len(sc), 1)).from_buffer_copy(sc.ljust(1, b"\0"))
+        info = _lib.VxgCompareBytesInfo()
+        _lib.check(ctx.lib.vxg_compare_bytes(ctx.handle, C.byref(node), _lib.CMP_OP[op], sbuf, len(sc), flags,
+                                             C.byref(out), C.byref(info), ctx.stream_ptr()))
+    else:
+        sc = np.array([scalar]).astype(NP_OF_PTYPE[a.ptype]).tobytes() if a.dtype == DTYPE["PRIMITIVE"] else bytes(8)
+        sbuf = (C.c_uint8 * 8)(*sc.ljust(8, b"\0")[:8])
+        info = _lib.VxgCompareInfo()
+        _lib.check(ctx.lib.vxg_compare_scalar(ctx.handle, C.byref(node), _lib.CMP_OP[op], sbuf, flags, C.byref(out),
+                                              C.byref(info), ctx.stream_ptr()))
     res = Canonical("bool", a.len, a.ptype, values=vals[:nbytes],
                     info={f: int(getattr(info, f)) for f, _ in info._fields_})
     if out.validity:

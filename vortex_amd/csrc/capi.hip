@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "compare.hpp"
+#include "compare_str.hpp"
 #include "encode_gpu.hpp"
 #include "filter.hpp"
 #include "k1g.hpp"
@@ -542,6 +543,9 @@ class Planner {
     // compute::compare with a scalar (compare.hip): a Bool canonical, bit i = op(value i, scalar)
     vxg_status compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
                        vxg_compare_info& info);
+    // compute::compare of a utf8/binary array with a scalar (compare_str.hip)
+    vxg_status compare_bytes(const vxg_array& a, int op, const void* scalar_host, uint64_t scalar_len, uint32_t flags,
+                             vxg_canonical& out, vxg_compare_bytes_info& info);
     vxg_status canonical_size(const vxg_array& a, uint64_t& vb, uint64_t& db);
     // Data buffers of a string canonical, placed 16-byte aligned in one allocation.
     vxg_status string_layout(const vxg_array& a, std::vector<vxg_data_buffer>& bufs, uint64_t& extent);
@@ -638,6 +642,16 @@ class Planner {
     };
     vxg_status compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused);
     vxg_status launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op);
+    // The string pieces of one row-compare target (the output bitmap, or the truth tables of the
+    // Dict pieces), by kernel.
+    struct StrRows {
+        std::vector<VbDictPiece> vbd;
+        std::vector<VbPiece> vb;
+        std::vector<ViewPiece> vw;
+        std::vector<FsstPiece> fs;
+    };
+    vxg_status compare_rows_of(const vxg_array& s, uint64_t out_bit, bool excl, bool table, StrRows& rows, bool* fell_back);
+    vxg_status launch_str_rows(StrRows& rows, const StrScalar& sc, void* out, int op, uint32_t& launches);
     vxg_status validity_into(const vxg_array& a, void** bitmap);
     // OR the values of a Bool-dtype array into the zeroed bit buffer `bits` at bit `off`.
     vxg_status bools_into(const vxg_array& a, void* bits, uint64_t off);
@@ -1615,6 +1629,395 @@ vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, ui
         VXG_TRY(launch_cmp_plain(a.ptype, pv, p->len, out.values, ob, scalar_bits, op, word_edges(ob, p->len), s_));
         info.fallback_arrays++;
     }
+
+    // value bits of null rows are 0; null_as_false drops the validity (filtering.rs:42)
+    const vxg_array* vnode;
+    int vkind;
+    VXG_TRY(validity_source(a, &vnode, &vkind));
+    const bool null_as_false = (flags & VXG_CMP_NULL_AS_FALSE) != 0;
+    if (vkind == 0) {
+        out.validity = nullptr;
+        return VXG_OK;
+    }
+    void* vbits = nullptr;
+    if (null_as_false) VXG_TRY(temp(bytes, &vbits));
+    else if (out.validity) vbits = out.validity;
+    else {
+        VXG_TRY(hip_check(hipMalloc(&vbits, bytes ? bytes : 8), "compare validity alloc"));
+        out.validity = vbits;  // (the entry point releases it if a later step fails)
+    }
+    if (reinterpret_cast<uintptr_t>(vbits) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare validity must be 8-byte aligned");
+    if (n) {  // (an empty array's bitmaps hold no bytes: nothing is written)
+        VXG_TRY(launch_copy_bytes(vbits, nullptr, bytes, s_));
+        VXG_TRY(validity_into(a, &vbits));
+        VXG_TRY(launch_and_words(out.values, vbits, words, s_));
+    }
+    out.validity = null_as_false ? nullptr : vbits;
+    return VXG_OK;
+}
+
+// ---- compute::compare of strings with a scalar (compare_str.hip) ---------------------------
+// The rows of string array `s` (a piece, or the values of a Dict piece) as a piece of the row
+// kernels, at bit out_bit of their target.  VarBin, VarBinView and FSST are read where they lie;
+// anything else is canonicalized into temporaries and compared as a VarBinView (*fell_back).
+// `table`: the target is a truth table (out_bit on a word, every word exclusive), so a VarBin
+// with plain offsets takes the 40-byte form.
+vxg_status Planner::compare_rows_of(const vxg_array& s, uint64_t out_bit, bool excl, bool table, StrRows& rows,
+                                    bool* fell_back) {
+    *fell_back = false;
+    if (s.dtype != VXG_DTYPE_UTF8 && s.dtype != VXG_DTYPE_BINARY)
+        return set_error(VXG_ERR_MISMATCHED_TYPES, "compare: expected a utf8 or binary array");
+    if (s.len == 0) return VXG_OK;
+    auto bytes_of = [&](const vxg_array& b, const void** p) -> vxg_status {
+        if (b.dtype != VXG_DTYPE_PRIMITIVE || width(b) != 1)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "string bytes must be a u8 array");
+        return view_primitive(b, p);
+    };
+    auto view_piece = [&](const void* views, const std::vector<StrBuf>& bufs) -> vxg_status {
+        if (reinterpret_cast<uintptr_t>(views) & 15)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views must be 16-byte aligned");
+        ViewPiece p{};
+        p.views = static_cast<const uint8_t*>(views);
+        p.n_buffers = uint32_t(bufs.size());
+        if (bufs.size() == 1) p.buf0 = bufs[0];
+        if (bufs.size() > 1) {  // a device table of the buffers, like Planner::filter's
+            void* d;
+            VXG_TRY(temp(bufs.size() * sizeof(StrBuf), &d));
+            VXG_TRY(hip_check(hipMemcpyAsync(d, bufs.data(), bufs.size() * sizeof(StrBuf), hipMemcpyHostToDevice, s_),
+                              "compare buffer table upload"));
+            VXG_TRY(hip_check(hipStreamSynchronize(s_), "compare buffer table sync"));  // `bufs` is read by the upload
+            p.bufs = static_cast<const StrBuf*>(d);
+        }
+        p.out_bit = out_bit;
+        p.n = s.len;
+        p.excl = excl;
+        rows.vw.push_back(p);
+        return VXG_OK;
+    };
+    switch (s.encoding) {
+    case VXG_ENC_VARBIN: {
+        const vxg_array* offs = child(s, 0);
+        const vxg_array* bytes = child(s, 1);
+        if (!offs || !bytes) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinArray needs offsets and bytes");
+        if (!ptype_is_int(offs->ptype) || offs->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "VarBin offsets must be integers");
+        if (offs->len < s.len + 1) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets shorter than len + 1");
+        const void* pb;
+        VXG_TRY(bytes_of(*bytes, &pb));
+        if (table && offs->encoding == VXG_ENC_PRIMITIVE && bytes->len <= 0xFFFFFFFFull && s.len <= 0xFFFFFFFFull &&
+            out_bit % 64 == 0 && out_bit / 64 <= 0xFFFFFFFFull) {
+            const void* po;
+            VXG_TRY(view_primitive(*offs, &po));
+            if (reinterpret_cast<uintptr_t>(po) % uint64_t(width(*offs)))
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets must be aligned to their width");
+            VbDictPiece p{};
+            p.bytes = static_cast<const uint8_t*>(pb);
+            p.offs = po;
+            p.bytes_len = uint32_t(bytes->len);
+            p.out_word = uint32_t(out_bit / 64);
+            p.n = uint32_t(s.len);
+            p.width = uint8_t(width(*offs));
+            p.sgn = ptype_is_signed(offs->ptype);
+            rows.vbd.push_back(p);
+            return VXG_OK;
+        }
+        IntCol oc;
+        VXG_TRY(int_column(*offs, oc));
+        if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets must be aligned to their width");
+        VbPiece p{};
+        p.bytes = static_cast<const uint8_t*>(pb);
+        p.bytes_len = bytes->len;
+        p.offs = to_ccol(oc);
+        p.out_bit = out_bit;
+        p.n = s.len;
+        p.excl = excl;
+        rows.vb.push_back(p);
+        return VXG_OK;
+    }
+    case VXG_ENC_VARBINVIEW: {
+        const vxg_array* vw = child(s, 0);
+        const uint32_t nb = s.meta.varbinview.n_buffers;
+        if (!vw || s.n_children < 1 + nb)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinViewArray: missing views/data buffers");
+        const void* pv;
+        VXG_TRY(bytes_of(*vw, &pv));
+        if (vw->len < 16 * s.len) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views shorter than 16 * len");
+        std::vector<StrBuf> bufs(nb);
+        for (uint32_t b = 0; b < nb; b++) {
+            const void* pb;
+            VXG_TRY(bytes_of(s.children[1 + b], &pb));
+            bufs[b] = StrBuf{static_cast<const uint8_t*>(pb), s.children[1 + b].len};
+        }
+        return view_piece(pv, bufs);
+    }
+    case VXG_ENC_FSST: {
+        const vxg_array* sym = child(s, 0);
+        const vxg_array* slen = child(s, 1);
+        const vxg_array* codes = child(s, 2);
+        const vxg_array* ulen = child(s, 3);
+        if (!sym || !slen || !codes || !ulen || codes->encoding != VXG_ENC_VARBIN || !child(*codes, 0) || !child(*codes, 1))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSSTArray needs symbols, lengths, VarBin codes, lengths");
+        if (sym->len > 255 || slen->len < sym->len || width(*sym) != 8 || width(*slen) != 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbol table must hold at most 255 u64 symbols and their u8 lengths");
+        if (codes->len != s.len || ulen->len < s.len || child(*codes, 0)->len < s.len + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST codes / lengths do not cover the array");
+        if (!ptype_is_int(child(*codes, 0)->ptype) || !ptype_is_int(ulen->ptype))
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "FSST offsets and lengths must be integers");
+        const void *psym, *pslen, *pcb;
+        VXG_TRY(view_primitive(*sym, &psym));
+        VXG_TRY(view_primitive(*slen, &pslen));
+        VXG_TRY(bytes_of(*child(*codes, 1), &pcb));
+        if (reinterpret_cast<uintptr_t>(psym) & 7) return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbols must be 8-byte aligned");
+        IntCol oc, lc;
+        VXG_TRY(int_column(*child(*codes, 0), oc));
+        VXG_TRY(int_column(*ulen, lc));
+        if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width) ||
+            reinterpret_cast<uintptr_t>(lc.p) % uint64_t(lc.packed ? 16 : lc.width))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST offsets / lengths must be aligned to their width");
+        FsstPiece p{};
+        p.symbols = static_cast<const uint64_t*>(psym);
+        p.sym_lens = static_cast<const uint8_t*>(pslen);
+        p.codes = static_cast<const uint8_t*>(pcb);
+        p.codes_len = child(*codes, 1)->len;
+        p.offs = to_ccol(oc);
+        p.lens = to_ccol(lc);
+        p.out_bit = out_bit;
+        p.n = s.len;
+        p.excl = excl;
+        p.n_symbols = uint32_t(sym->len);
+        rows.fs.push_back(p);
+        return VXG_OK;
+    }
+    default: {
+        // canonical views + data in temporaries (as Planner::filter builds its source)
+        *fell_back = true;
+        vxg_canonical src{};
+        std::vector<vxg_data_buffer> lay;
+        uint64_t extent;
+        VXG_TRY(string_layout(s, lay, extent));
+        const vxg_array* vnode;
+        int vkind;
+        VXG_TRY(validity_source(s, &vnode, &vkind));
+        if (vkind != 0) VXG_TRY(temp(((s.len + 31) / 32) * 4, &src.validity));
+        VXG_TRY(temp(16 * s.len, &src.views));
+        VXG_TRY(temp(extent + 16, &src.data));
+        src.data_bytes = extent;
+        src.data_buffers = lay.data();
+        src.n_data_buffers = src.data_buffers_cap = uint32_t(lay.size());
+        VXG_TRY(string_canonical(s, src));
+        std::vector<StrBuf> bufs(lay.size());
+        for (size_t b = 0; b < lay.size(); b++)
+            bufs[b] = StrBuf{static_cast<const uint8_t*>(src.data) + lay[b].offset, lay[b].len};
+        return view_piece(src.views, bufs);
+    }
+    }
+}
+
+// Every piece of `rows` into `out`: one launch per kind and per kernel-argument table.
+vxg_status Planner::launch_str_rows(StrRows& rows, const StrScalar& sc, void* out, int op, uint32_t& launches) {
+    uint32_t* err = ctx_->c.err_word;
+    auto run = [&](auto& v, auto tab, auto groups_of, auto launch) -> vxg_status {
+        constexpr size_t cap = sizeof(tab.c) / sizeof(tab.c[0]);
+        for (size_t i = 0; i < v.size(); i += cap) {
+            tab.n = 0;
+            uint64_t groups = 0;
+            for (size_t k = i; k < v.size() && k < i + cap; k++) {
+                v[k].first_group = uint32_t(groups);
+                groups += groups_of(v[k]);
+                tab.c[tab.n++] = v[k];
+            }
+            VXG_TRY(launch(tab, groups));
+            launches++;
+        }
+        return VXG_OK;
+    };
+    VXG_TRY(run(rows.vbd, VbDictTab{}, [](const VbDictPiece& p) { return piece_groups(0, p.n); },
+                [&](const VbDictTab& t, uint64_t g) { return launch_cmpb_varbin_dict(t, g, sc, out, err, op, s_); }));
+    VXG_TRY(run(rows.vb, VbTab{}, [](const VbPiece& p) { return piece_groups(p.out_bit, p.n); },
+                [&](const VbTab& t, uint64_t g) { return launch_cmpb_varbin(t, g, sc, out, err, op, s_); }));
+    VXG_TRY(run(rows.vw, ViewTab{}, [](const ViewPiece& p) { return piece_groups(p.out_bit, p.n); },
+                [&](const ViewTab& t, uint64_t g) { return launch_cmpb_views(t, g, sc, out, err, op, s_); }));
+    VXG_TRY(run(rows.fs, FsstTab{}, [](const FsstPiece& p) { return piece_groups(p.out_bit, p.n); },
+                [&](const FsstTab& t, uint64_t g) { return launch_cmpb_fsst(t, g, sc, out, err, op, s_); }));
+    return VXG_OK;
+}
+
+vxg_status Planner::compare_bytes(const vxg_array& a, int op, const void* scalar_host, uint64_t scalar_len, uint32_t flags,
+                                  vxg_canonical& out, vxg_compare_bytes_info& info) {
+    if (a.dtype != VXG_DTYPE_UTF8 && a.dtype != VXG_DTYPE_BINARY)
+        return set_error(VXG_ERR_MISMATCHED_TYPES, "compare_bytes needs a utf8 or binary array");
+    if (op < VXG_CMP_EQ || op > VXG_CMP_LTE)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare operator " + std::to_string(op));
+    if (flags & ~uint32_t(VXG_CMP_NULL_AS_FALSE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare flags");
+    if (a.len > kCmpMaxLen) return set_error(VXG_ERR_INVALID_ARGUMENT, "array too long for one compare launch");
+    const uint64_t n = a.len, words = (n + 63) / 64, bytes = words * 8;
+
+    // the pieces: the array itself, or the chunks of a top-level ChunkedArray at their bit offsets
+    std::vector<std::pair<const vxg_array*, uint64_t>> pieces;
+    if (a.encoding == VXG_ENC_CHUNKED) {
+        if (a.n_children != a.meta.chunked.nchunks + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked child count != nchunks + 1");
+        uint64_t off = 0;
+        for (uint32_t i = 1; i < a.n_children; i++) {
+            const vxg_array& c = a.children[i];
+            if (c.dtype != a.dtype) return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the same dtype");
+            pieces.emplace_back(&c, off);
+            off += c.len;
+        }
+        if (off != n) return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked chunk lengths do not sum to len");
+    } else {
+        pieces.emplace_back(&a, 0);
+    }
+
+    // classify and validate every piece before the output is allocated or a compare is launched
+    struct DictPacked {
+        int T;
+        CmpChunk d;
+        bool excl;
+    };
+    StrRows table_rows, out_rows;
+    std::vector<DictPacked> packed;
+    std::vector<DictPlainPiece> plain;
+    uint64_t tt_words = 0;
+    bool zero = false;  // some word is ORed in: the bitmap starts zeroed
+    auto word_edges = [&](uint64_t ob, uint64_t len) { return ob % 64 == 0 && ((ob + len) % 64 == 0 || ob + len == n); };
+    for (const auto& [p, ob] : pieces) {
+        const bool edges = word_edges(ob, p->len);
+        bool fell = false;
+        if (p->encoding != VXG_ENC_DICT) {
+            VXG_TRY(compare_rows_of(*p, ob, edges, false, out_rows, &fell));
+            if (fell) info.fallback_arrays++;
+            else info.direct_chunks++;
+            zero = zero || (p->len && !edges);
+            continue;
+        }
+        const vxg_array* values = child(*p, 0);
+        const vxg_array* codes = child(*p, 1);
+        if (!values || !codes) return set_error(VXG_ERR_INVALID_ARGUMENT, "DictArray needs values and codes");
+        if (!ptype_is_int(codes->ptype) || codes->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "Dict codes must be integers");
+        if (codes->len != p->len) return set_error(VXG_ERR_INVALID_ARGUMENT, "Dict codes length != array length");
+        if (values->len > 0xFFFFFFFFull) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare: dictionary of 2^32 or more values");
+        info.dict_chunks++;
+        if (p->len == 0) continue;  // an empty chunk: counted, nothing to launch
+        const uint64_t tword = tt_words;
+        if (tword > 0xFFFFFFFFull) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare: truth tables exceed 2^32 words");
+        tt_words += std::max<uint64_t>(1, (values->len + 63) / 64);
+        // (a) the truth table: the dictionary's values, compared like any string array
+        VXG_TRY(compare_rows_of(*values, tword * 64, true, true, table_rows, &fell));
+        if (fell) info.fallback_arrays++;
+        // (b) the lookup
+        const int T = 8 * width(*codes);
+        if (codes->encoding == VXG_ENC_FL_BITPACKED && ptype_is_unsigned(codes->ptype) && !codes->meta.bitpacked.has_patches) {
+            const vxg_buffer* pb = buf(*codes, 0);
+            const unsigned W = codes->meta.bitpacked.bit_width, off = codes->meta.bitpacked.offset;
+            if (off > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
+            if (W > unsigned(T)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
+            const uint64_t nblk = (p->len + off + 1023) / 1024, have = pb ? pb->len : 0;
+            if (W > 0 && have != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
+                                                               " packed bytes, got " + std::to_string(have));
+            if (W > 0 && (reinterpret_cast<uintptr_t>(pb->ptr) & 15))
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "packed buffer must be 16-byte aligned");
+            DictPacked dp{};
+            dp.T = T;
+            dp.d.packed = pb ? static_cast<const uint8_t*>(pb->ptr) : nullptr;
+            dp.d.reference = tword | uint64_t(values->len) << 32;
+            dp.d.out_bit = ob;
+            dp.d.len_lo = uint32_t(p->len);
+            dp.d.len_hi = uint8_t(p->len >> 32);
+            dp.d.offset = uint16_t(off);
+            dp.d.W = uint8_t(W);
+            dp.excl = edges && off % 64 == 0;
+            zero = zero || !dp.excl;
+            packed.push_back(dp);
+        } else {  // a Primitive array in place; any other encoding through a temporary
+            const void* pc;
+            VXG_TRY(view_primitive(*codes, &pc));
+            if (reinterpret_cast<uintptr_t>(pc) % uint64_t(width(*codes)))
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "primitive buffer must be aligned to the value width");
+            DictPlainPiece d{};
+            d.codes = pc;
+            d.out_bit = ob;
+            d.n = p->len;
+            d.tword = uint32_t(tword);
+            d.vlen = uint32_t(values->len);
+            d.width = uint8_t(width(*codes));
+            d.sgn = ptype_is_signed(codes->ptype);
+            d.excl = edges;
+            zero = zero || !edges;
+            plain.push_back(d);
+        }
+    }
+
+    // the scalar: short ones ride in the kernel argument, long ones go to a temporary
+    StrScalar sc{};
+    sc.len = scalar_len;
+    if (scalar_len <= kStrInline) {
+        if (scalar_len) std::memcpy(sc.inl, scalar_host, size_t(scalar_len));
+    } else {
+        void* d;
+        VXG_TRY(temp(scalar_len, &d));
+        VXG_TRY(hip_check(hipMemcpyAsync(d, scalar_host, scalar_len, hipMemcpyHostToDevice, s_), "compare scalar upload"));
+        VXG_TRY(hip_check(hipStreamSynchronize(s_), "compare scalar sync"));  // the caller may free its bytes
+        sc.dev = static_cast<const uint8_t*>(d);
+    }
+
+    out.kind = VXG_ENC_BOOL;
+    out.len = n;
+    out.dtype = VXG_DTYPE_BOOL;
+    out.ptype = VXG_U8;
+    out.values_bytes = bytes;
+    if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, bytes ? bytes : 8), "compare values alloc"));
+    if (reinterpret_cast<uintptr_t>(out.values) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare output must be 8-byte aligned");
+    if (zero) VXG_TRY(launch_copy_bytes(out.values, nullptr, bytes, s_));
+
+    // truth tables: every dictionary starts on a 64-bit word of one temporary
+    void* tt = nullptr;
+    if (tt_words) {
+        VXG_TRY(temp(tt_words * 8, &tt));
+        VXG_TRY(launch_str_rows(table_rows, sc, tt, op, info.table_launches));
+    }
+    // lookups of the BitPacked codes, one launch per code width T
+    std::stable_sort(packed.begin(), packed.end(), [](const DictPacked& x, const DictPacked& y) { return x.T < y.T; });
+    for (size_t i = 0; i < packed.size();) {
+        size_t j = i;
+        uint64_t blocks = 0;
+        while (j < packed.size() && j - i < size_t(kCmpArgChunks) && packed[j].T == packed[i].T) blocks += packed[j++].d.n_blocks();
+        uint32_t pick = uint32_t(std::min<uint64_t>(32, blocks / 1024)) & ~3u;  // launch_compare_group's rule
+        if (pick < 4) pick = 4;
+        CmpTable tab{};
+        uint64_t groups = 0;
+        uint32_t lds = 0;
+        for (size_t k = i; k < j; k++) {
+            CmpChunk& c = tab.c[tab.n++];
+            c = packed[k].d;
+            const uint32_t bpw = std::min(cmp_bpw_max(c.W), pick);
+            c.bpw_excl = uint8_t(bpw | (packed[k].excl ? 0x80u : 0u));
+            c.first_group = uint32_t(groups);
+            groups += (c.n_blocks() + bpw - 1) / bpw;
+            lds = std::max(lds, bpw * 128u * c.W);
+        }
+        VXG_TRY(launch_cmpb_dict_packed(packed[i].T, tab, groups, lds + 128, out.values, tt, ctx_->c.err_word, s_));
+        info.dict_launches++;
+        i = j;
+    }
+    for (size_t i = 0; i < plain.size(); i += size_t(kStrArgPieces40)) {
+        DictPlainTab tab{};
+        uint64_t groups = 0;
+        for (size_t k = i; k < plain.size() && k < i + size_t(kStrArgPieces40); k++) {
+            plain[k].first_group = uint32_t(groups);
+            groups += piece_groups(plain[k].out_bit, plain[k].n);
+            tab.c[tab.n++] = plain[k];
+        }
+        VXG_TRY(launch_cmpb_dict_plain(tab, groups, out.values, tt, ctx_->c.err_word, s_));
+        info.dict_launches++;
+    }
+    // VarBin / VarBinView / FSST pieces in place, and the canonicalized ones
+    VXG_TRY(launch_str_rows(out_rows, sc, out.values, op, info.direct_launches));
 
     // value bits of null rows are 0; null_as_false drops the validity (filtering.rs:42)
     const vxg_array* vnode;
@@ -3079,6 +3482,25 @@ vxg_status vxg_compare_scalar(vxg_ctx* ctx, const vxg_array* a, int op, const vo
     void* const values_in = out->values;
     void* const validity_in = out->validity;
     const vxg_status st = p.compare(*a, op, bits, flags, *out, ci);
+    if (info) *info = ci;
+    if (st != VXG_OK) {  // nothing engine-allocated is handed back with an error
+        if (out->values && out->values != values_in) (void)hipFree(out->values);
+        if (out->validity && out->validity != validity_in) (void)hipFree(out->validity);
+        out->values = values_in;
+        out->validity = validity_in;
+    }
+    return st;
+}
+
+vxg_status vxg_compare_bytes(vxg_ctx* ctx, const vxg_array* a, int op, const void* scalar_host, uint64_t scalar_len,
+                             uint32_t flags, vxg_canonical* out, vxg_compare_bytes_info* info, void* stream) {
+    VXG_TRY(use_device(ctx));
+    if (!a || !out || (scalar_len && !scalar_host)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null array/scalar/out");
+    vxg_compare_bytes_info ci{};
+    Planner p(ctx, S(stream));
+    void* const values_in = out->values;
+    void* const validity_in = out->validity;
+    const vxg_status st = p.compare_bytes(*a, op, scalar_host, scalar_len, flags, *out, ci);
     if (info) *info = ci;
     if (st != VXG_OK) {  // nothing engine-allocated is handed back with an error
         if (out->values && out->values != values_in) (void)hipFree(out->values);
