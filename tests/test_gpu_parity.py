@@ -28,8 +28,9 @@ def gpu(arr, ctx):
     return V.canonicalize(dev, ctx)
 
 
-def assert_primitive_parity(arr, ctx, expect=None):
-    res = gpu(arr, ctx)
+def assert_primitive_parity(arr, ctx, expect=None, res=None):
+    """`res`: a result to check (a plan's) instead of a vxg_canonicalize of `arr`."""
+    res = gpu(arr, ctx) if res is None else res
     got = res.numpy()
     ref, rvalid = canon(arr)
     assert got.dtype == ref.dtype and got.size == ref.size
@@ -44,8 +45,8 @@ def assert_primitive_parity(arr, ctx, expect=None):
     return got
 
 
-def assert_string_parity(arr, ctx, strings=None):
-    res = gpu(arr, ctx)
+def assert_string_parity(arr, ctx, strings=None, res=None):
+    res = gpu(arr, ctx) if res is None else res
     views, _ = res.numpy()
     heap = res.buffers()
     (rviews, rheap), rvalid = canon(arr)
@@ -1193,7 +1194,7 @@ def sys_path_bench():
 
 
 class plan_mode:
-    """VXG_PLAN_BATCH for the plans created inside (capi.hip reads it at every vxg_plan_create):
+    """VXG_PLAN_BATCH for the plans created inside (plan.hip reads it at every vxg_plan_create):
     "0" unbatched, "1" batched, "mixed", None = the default (plain create: the batched
     candidate; measure=True: both recorded, vxg_plan_select keeps one)."""
 
@@ -1485,6 +1486,66 @@ def test_plan_string_dict_job_lookup(ctx, sizes):
     assert res.numpy()[0].tobytes() == rviews.tobytes()
     assert [b.tobytes() for b in res.buffers()] == [b.tobytes() for b in rbufs]
     plan.close()
+
+
+def _table_edge_chunk(shape, rng, n):
+    """One tiny chunk of `n` values (n = 0: a zero-length chunk) of a single kernel group, and its
+    plain values."""
+    if shape == "k1":  # BitPacked u32, every chunk W = 9: two FastLanes blocks
+        v = rng.integers(0, 1 << 9, n, dtype=np.uint64).astype(np.uint32)
+        return E.encode_bitpacked(v, bit_width=9, allow_patches=False), v
+    if shape == "runend_short":  # ~100 runs of 1-5 rows: the thread-per-run kernel
+        v = np.repeat(rng.integers(-1000, 1000, 100), rng.integers(1, 6, 100))[:n].astype(np.int32)
+        return E.encode_runend(v), v
+    if shape == "runend_long":  # ~100 runs of 40-60 rows: the workgroup-per-span kernel
+        v = np.repeat(rng.integers(-1000, 1000, 100), rng.integers(40, 61, 100))[:n].astype(np.int32)
+        return E.encode_runend(v), v
+    words = [b"DELIVER IN PERSON", b"NONE", b"a string of more than twelve bytes"]
+    s = [words[i] for i in np.concatenate([np.arange(3), rng.integers(0, 3, max(n - 3, 0))])[:n]]
+    return E.encode_dict_strings(s), s
+
+
+# kernel-argument capacity of the shape's chunk table (vxg_internal.hpp: kArgChunks,
+# kRunEndArgChunks, kVarBinArgChunks) and the rows of one chunk
+_TABLE_EDGE = {"k1": (32, 1030), "runend_short": (32, 10 ** 6), "runend_long": (32, 10 ** 6), "dict_strings": (48, 100)}
+
+
+@pytest.mark.parametrize("extra", [0, 2], ids=["empties_counted", "empties_extra"])
+@pytest.mark.parametrize("count", ["N", "N+1", "2N+1"])
+@pytest.mark.parametrize("shape", list(_TABLE_EDGE))
+def test_chunk_table_edges(ctx, shape, count, extra):
+    """The chunk-table rule at its edges (chunk_pack.hpp): Chunked arrays of exactly N, N + 1 and
+    2N + 1 chunks of ONE kernel group, N = the table's kernel-argument capacity, with two
+    zero-length chunks among them (one in the middle, one last) -- counted in the N
+    (`empties_counted`) or on top of N non-empty chunks (`empties_extra`: K1 and RunEnd keep empty
+    chunks out of their tables, so this is the variant that fills those exactly).  vxg_canonicalize
+    splits at N per launch; an unbatched plan takes one launch over a device table above N; a
+    batched plan moves the small groups into its K1g launch.  Dict(VarBin) dictionaries this small
+    are built inside K1g by every plan, so the unbatched plan is also recorded with
+    VXG_PLAN_VB_K1G=0, which sends them through the VarBin table.  Every way is bit-exact against
+    the oracle (which canonicalizes zero-length chunks of all three encodings)."""
+    cap, rows = _TABLE_EDGE[shape]
+    total = {"N": cap, "N+1": cap + 1, "2N+1": 2 * cap + 1}[count] + extra
+    rng = np.random.default_rng(4242)
+    chunks, expect = [], []
+    for k in range(total):
+        arr, v = _table_edge_chunk(shape, rng, 0 if k in (total // 2, total - 1) else rows)
+        chunks.append(arr)
+        expect.append(v)
+    arr = A.chunked(chunks)
+    if shape == "dict_strings":
+        strings = [s for e in expect for s in e]
+        check = lambda res=None: assert_string_parity(arr, ctx, strings, res=res)
+    else:
+        check = lambda res=None: assert_primitive_parity(arr, ctx, np.concatenate(expect), res=res)
+    check()  # vxg_canonicalize
+    dev = arr.to(torch_dev())
+    ways = [("0", {}), ("1", {})] + ([("0", {"VXG_PLAN_VB_K1G": "0"})] if shape == "dict_strings" else [])
+    for mode, env in ways:
+        with plan_mode(mode), env_set(**env):
+            plan = V.Plan([dev], ctx)
+        check(plan.launch(sync=True)[0])
+        plan.close()
 
 
 @pytest.mark.parametrize("mode", ["0", "1"])

@@ -70,7 +70,7 @@ def main():
     if len(fseg) != len(cols) or len(wseg) != len(cols):
         raise SystemExit(f"{len(cols)} columns but {len(fseg)} / {len(wseg)} marked segments")
     # direct steps + plan replays (warm-ups included) + the plan's selection replays (2 candidates
-    # x (1 warm-up + 3 timed), capi.hip vxg_plan_create)
+    # x (1 warm-up + 3 timed), plan.hip vxg_plan_create)
     steps = 2 * (3 + a.cols_reps) + 8
     out = {"correction": "bytes = (2 * FETCH_SIZE + WRITE_SIZE) KiB * 1024 (gfx950, MI355X_MICROARCH.md §HBM)",
            "columns": []}

@@ -1,5 +1,5 @@
-// dict_rows.hip — K14: Dict(codes = BitPacked) canonicalize for wide dictionary values (8-byte
-// primitives, 16-byte BinaryViews of a string dictionary), thread per output value.
+// dict_rows.hip — K14: Dict(codes = BitPacked) canonicalize for 16-byte dictionary values (the
+// BinaryViews of a string dictionary), thread per output value.
 //
 // Reference: DictArray::into_canonical = take(values.into_canonical(), codes)
 // (encodings/dict/src/array.rs:68-73; primitive/compute/take.rs:58-67; varbinview/compute.rs:
@@ -25,7 +25,6 @@ constexpr int kRowsThreads = 256;
 constexpr int kRowsMaxW = 16;  // codes bit width (kDictFusedMaxW)
 
 template <int VW> struct DVal;
-template <> struct DVal<8> { using t = uint64_t; };
 template <> struct DVal<16> { using t = uint4; };
 
 template <int T, int VW, int BPW, bool LDSD, bool EXT>
@@ -121,14 +120,15 @@ vxg_status launch_rows_t(const ChunkTable& tab, unsigned W, hipStream_t s) {
 
 }  // namespace
 
-vxg_status launch_dict_rows(int T, int W, int vw, const ChunkTable& tab, hipStream_t s) {
+vxg_status launch_dict_rows(int T, int W, const ChunkTable& tab, hipStream_t s) {
     if (W < 0 || W > kRowsMaxW || W > T) return VXG_ERR_NOT_IMPLEMENTED;
     const unsigned w = unsigned(W);
-#define VXG_ROWS(TT, VV) \
-    if (T == TT && vw == VV) return launch_rows_t<TT, VV>(tab, w, s);
-    VXG_ROWS(8, 8) VXG_ROWS(16, 8) VXG_ROWS(32, 8) VXG_ROWS(64, 8)
-    VXG_ROWS(8, 16) VXG_ROWS(16, 16) VXG_ROWS(32, 16) VXG_ROWS(64, 16)
-#undef VXG_ROWS
+    switch (T) {
+    case 8: return launch_rows_t<8, 16>(tab, w, s);
+    case 16: return launch_rows_t<16, 16>(tab, w, s);
+    case 32: return launch_rows_t<32, 16>(tab, w, s);
+    case 64: return launch_rows_t<64, 16>(tab, w, s);
+    }
     return VXG_ERR_NOT_IMPLEMENTED;
 }
 

@@ -225,7 +225,7 @@ template <> struct AlpT<float> {
     __device__ static float sub(float a, float b) { return __fsub_rn(a, b); }
 };
 
-// F10 / IF10 (alp/mod.rs:255-351, the engine's copies in capi.hip) by value
+// F10 / IF10 (alp/mod.rs:255-351, the engine's copies in capi.hip's ALP tables) by value
 template <typename F> struct AlpTables { F f10[24]; F if10[24]; };
 
 // Rust `as` float -> int: saturating, NaN -> 0

@@ -1,4 +1,4 @@
-// encode_gpu.hpp — launchers of the GPU encoders (encode_gpu.hip, pack_inst.hip); C ABI in capi.hip.
+// encode_gpu.hpp — launchers of the GPU encoders (encode_gpu.hip, pack_inst.hip); their C entry points are in capi.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

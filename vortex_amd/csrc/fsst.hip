@@ -1156,21 +1156,14 @@ bool with_acc(int kind, F&& f) {
 // Extra (unused) dynamic LDS per decode workgroup, VXG_FSST_PAD_LDS bytes (diagnostics: the
 // occupancy sensitivity of the decode -- 16 KiB more leaves 4 instead of 8 workgroups per CU).
 static size_t fsst_pad_lds() {
-    static const size_t v = [] {
-        const char* e = std::getenv("VXG_FSST_PAD_LDS");
-        const long x = e ? std::strtol(e, nullptr, 10) : 0;
-        return size_t(x > 0 && x <= 65536 ? x : 0);
-    }();
+    static const size_t v = size_t(env_int("VXG_FSST_PAD_LDS", 1, 65536, 0));
     return v;
 }
 
 // Called by every vxg_open after its device is selected: the mask is parsed once per process,
 // copied to each context's device (g_fsst_abl is per device).
 hipError_t fsst_diag_init() {
-    static const uint32_t m = [] {
-        const char* e = std::getenv("VXG_FSST_ABL");
-        return e ? uint32_t(std::strtoul(e, nullptr, 10)) : 0u;
-    }();
+    static const uint32_t m = uint32_t(env_u64("VXG_FSST_ABL", 0));
     return m ? hipMemcpyToSymbol(HIP_SYMBOL(g_fsst_abl), &m, sizeof m) : hipSuccess;
 }
 
@@ -1182,11 +1175,7 @@ static bool fused_acc(int oa, int la) { return (oa == 32 && la == 32) || (oa == 
 // Percentage of the K1g workgroups interleaved with the decode tiles (VXG_FUSED_MIX, 0-100,
 // read once; default 100: the tiles spread over the whole grid).
 static uint64_t fused_mix_pct() {
-    static const uint64_t v = [] {
-        const char* e = std::getenv("VXG_FUSED_MIX");
-        const long x = e ? std::strtol(e, nullptr, 10) : 100;
-        return uint64_t(x >= 0 && x <= 100 ? x : 100);
-    }();
+    static const uint64_t v = uint64_t(env_int("VXG_FUSED_MIX", 0, 100, 100));
     return v;
 }
 
@@ -1199,15 +1188,9 @@ static uint64_t fused_mix_pct() {
 // 0.0745 -> 0.0735 (0.0803); 2-GPU (11,720) 0.1454 -> 0.1475; 1 GPU (23,443) 0.272 -> 0.280-0.288
 // (not because of the device-scope record loads: plain first reads of parity-alternated record
 // buffers measured the same, profiles/r06_fsst_decode.md).
-static uint64_t fused_prepass_max_tiles() {
-    const char* e = std::getenv("VXG_FUSED_PREPASS_MAX_TILES");
-    return e ? uint64_t(std::strtoull(e, nullptr, 10)) : uint64_t(8192);
-}
+static uint64_t fused_prepass_max_tiles() { return env_u64("VXG_FUSED_PREPASS_MAX_TILES", 8192); }
 static int64_t fused_delay() {
-    static const int64_t v = [] {
-        const char* e = std::getenv("VXG_FUSED_DELAY");
-        return e ? int64_t(std::strtoull(e, nullptr, 10)) : int64_t(-1);
-    }();
+    static const int64_t v = int64_t(env_u64("VXG_FUSED_DELAY", uint64_t(-1)));
     return v;
 }
 

@@ -57,11 +57,7 @@ int gen_kind(int T, int epi, int vw, bool varbin_dict) {
 // Blocks per K1g workgroup: as many as kGenPackedLds of packed words hold, at most the launch's
 // cap (gen_bpw_cap; VXG_K1G_BPW, read once, fixes it for every launch).
 static long gen_bpw_env() {
-    static const long v = [] {
-        const char* e = std::getenv("VXG_K1G_BPW");
-        const long x = e ? std::strtol(e, nullptr, 10) : 0;
-        return x >= 1 && x <= 32 ? x : 0L;
-    }();
+    static const long v = long(env_int("VXG_K1G_BPW", 1, 32, 0));
     return v;
 }
 
@@ -90,10 +86,7 @@ uint32_t gen_bpw(int T, int W, uint32_t cap) {
 // profiles/r04_ubench_views.txt) -- while beside FSST tiles in the fused launch 4 blocks stay
 // best (C5 1 GPU 0.272-0.280 ms with 4 and 2, 0.305 with 1; session r06k).
 uint32_t gen_vb_bpw(int T, int W, bool alone, uint32_t cap) {
-    static const long v = [] {
-        const char* e = std::getenv("VXG_K1G_VB_BPW");
-        return e ? std::strtol(e, nullptr, 10) : 0L;
-    }();
+    static const long v = long(env_int("VXG_K1G_VB_BPW", 1, INT64_MAX, 0));
     // (VXG_K1G_VB_BPW set: that many blocks, above the launch's cap too, as LDS allows)
     const uint32_t b = gen_bpw(T, W, v >= 1 && uint32_t(v) > cap ? uint32_t(v) : cap);
     const uint32_t want = v >= 1 ? uint32_t(v) : (alone ? 1u : b);

@@ -1,0 +1,235 @@
+// planner.hpp — what the units of the canonicalize planner share: the Planner class, the K1 job and
+// plan-batch records, the launch-grouping functions and the small helpers of every entry point.
+//
+// The planner is the host-side mirror of the reference's dispatch: Array::into_canonical
+// (vortex-array/src/canonical.rs:353-357) -> ArrayEncoding::canonicalize (encoding/mod.rs:53)
+// -> per-encoding IntoCanonical.  Where the reference materialises one buffer per cascade
+// level (e.g. ALP -> FoR -> BitPacked is 3-4 passes, SURVEY.md §3 stack B) the planner
+// recognises the cascade and issues ONE fused K1 launch (+ tiny patch scatters); anything it
+// does not recognise is decoded child-first into temporaries exactly like the reference.
+//
+// Units: planner_launch.hip (launch grouping, K1 dispatch), planner_decode.hip (primitives,
+// validity, bools, canonical()), planner_strings.hip, planner_compute.hip (take, filter, compare),
+// plan.hip (the plan recorder), capi.hip (the context and the C entry points).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "compare.hpp"
+#include "compare_str.hpp"
+#include "env.hpp"
+#include "take.hpp"
+#include "vxg_internal.hpp"
+
+struct vxg_ctx {
+    vxg::Ctx c;
+};
+
+#define VXG_TRY(expr)                         \
+    do {                                      \
+        vxg_status _s = (expr);               \
+        if (_s != VXG_OK) return _s;          \
+    } while (0)
+
+namespace vxg {
+
+inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
+
+// Every entry point that takes a context starts here: its launches follow ctx's device and
+// options (g_cur_ctx, vxg_internal.hpp).  The error text of a failed call is this host thread's
+// (set_error; read back by vxg_last_error).
+vxg_status use_device(vxg_ctx* ctx);
+// The device error word's bits -> the VortexError variant each one stands for.
+vxg_status status_of_err_word(uint32_t err);
+
+inline bool is_string(const vxg_array& a) { return a.dtype == VXG_DTYPE_UTF8 || a.dtype == VXG_DTYPE_BINARY; }
+
+// One K1 decode (a whole BitPacked-rooted cascade of one array or one chunk) and the kernel
+// it needs.  Jobs with the same kernel share launches.
+struct K1Job {
+    int T, W;
+    Epi epi;
+    int vw;
+    ChunkDev d;
+    // a plan batch's Dict over a small VarBin dictionary: K1g builds the dictionary's views
+    // (d.dict unused) and copies its bytes (vb.src -> vb.dst); only K1g runs such a job
+    bool vb = false;
+    VarBinChunk vbc{};
+};
+
+// A recorded plan's deferred launches, shared by the planners of all its arrays: the K1 decodes,
+// RunEnd expansions and string-dictionary views of every chunked column, launched together at
+// the end of recording on one graph branch (dictionary views, then one launch per large K1 kernel
+// group + one K1g launch for all the small ones, then the expansions), instead of per column.
+struct PlanBatch {
+    struct Run {
+        int w;             // value width
+        RunEndChunk c;
+        bool indep;        // ends/values read in place (no K1 decode of this batch feeds it)
+    };
+    std::vector<VarBinChunk> dicts;
+    std::vector<K1Job> jobs;
+    std::vector<Run> runs;
+    std::vector<FsstChunk> fssts;  // FSST chunks of chunked columns
+    bool empty() const { return dicts.empty() && jobs.empty() && runs.empty() && fssts.empty(); }
+};
+
+// ---- launch grouping (planner_launch.hip) ---------------------------------------------------
+// Validate one BitPacked buffer (bitpacking/mod.rs:54-130) and describe its K1 decode.
+vxg_status make_k1_job(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
+                       Epi epi, int vw, const UnpackArgs& a, void* out, K1Job& j);
+// K1 jobs grouped by kernel; dt: the plan being recorded; generic_small: a plan's batch, whose
+// small groups share one K1g launch with gen_runs and the fused FSST group.
+vxg_status launch_k1_jobs(std::vector<K1Job>& jobs, uint32_t* err, hipStream_t s, DevTables* dt = nullptr,
+                          bool generic_small = false,
+                          const std::vector<std::pair<int, RunEndChunk>>* gen_runs = nullptr,
+                          const PatchCol* patch = nullptr, const FsstFused* fuse = nullptr);
+vxg_status launch_runs(std::vector<RunEndChunk> runs, int w, uint32_t* err, hipStream_t s, DevTables* dt);
+vxg_status launch_varbin_dicts(const std::vector<VarBinChunk>& dicts, uint32_t* err, hipStream_t s, DevTables* dt);
+vxg_status flush_plan_batch(PlanBatch& b, uint32_t* err, hipStream_t s, DevTables* dt);
+
+// ===================================================================================
+// Planner
+// ===================================================================================
+class Planner {
+  public:
+    Planner(vxg_ctx* ctx, hipStream_t s, DevTables* plan = nullptr, PlanBatch* batch = nullptr)
+        : ctx_(ctx), s_(s), plan_(plan), batch_(batch) {}
+    ~Planner() {
+        for (void* p : temps_) (void)hipFreeAsync(p, s_);
+    }
+
+    vxg_status canonical(const vxg_array& a, vxg_canonical& out);
+    // compute::take on the compressed tree (take.hip): values + validity.take(indices)
+    vxg_status take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out);
+    // compute::filter (filter.hip): the rows whose predicate bit is set + validity.filter
+    vxg_status filter(const vxg_array& a, const vxg_array& pred, vxg_canonical& out);
+    // compute::compare with a scalar (compare.hip): a Bool canonical, bit i = op(value i, scalar)
+    vxg_status compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
+                       vxg_compare_info& info);
+    // compute::compare of a utf8/binary array with a scalar (compare_str.hip)
+    vxg_status compare_bytes(const vxg_array& a, int op, const void* scalar_host, uint64_t scalar_len, uint32_t flags,
+                             vxg_canonical& out, vxg_compare_bytes_info& info);
+    vxg_status canonical_size(const vxg_array& a, uint64_t& vb, uint64_t& db);
+    // Data buffers of a string canonical, placed 16-byte aligned in one allocation.
+    vxg_status string_layout(const vxg_array& a, std::vector<vxg_data_buffer>& bufs, uint64_t& extent);
+    static vxg_status string_buffer_count(const vxg_array& a, uint32_t& n);
+
+  private:
+    vxg_ctx* ctx_;
+    hipStream_t s_;
+    std::vector<void*> temps_;
+    // Recording a plan: temporaries are plain allocations owned by the plan (alive for all its
+    // replays) instead of stream-ordered ones, and chunk tables longer than a kernel argument
+    // holds become device tables (one launch per kernel group).
+    DevTables* plan_ = nullptr;
+    PlanBatch* batch_ = nullptr;  // a plan's deferred launches (all its arrays), or null
+    // The array canonical() was called on.  Only a ChunkedArray that IS this root defers its
+    // launches into batch_: its chunks write straight into the caller's output and nothing
+    // recorded after it reads them.  A nested ChunkedArray (Dict values, FoR/ZigZag/ALP child,
+    // Sparse/RunEnd children, views of a string dictionary) feeds a consumer recorded right
+    // after it, so it launches immediately.
+    const vxg_array* root_ = nullptr;
+    bool defer(const vxg_array& a) const { return batch_ && &a == root_; }
+    // Deferred K1 decodes of the chunks of a ChunkedArray (grouped into shared launches) and
+    // the patch scatters that must follow them; null = launch immediately.
+    struct PatchJob {
+        const vxg_array* sp;
+        int T;
+        Epi epi;
+        int vw;
+        UnpackArgs a;
+        void* dst;
+        uint64_t out_len;
+    };
+    std::vector<K1Job>* k1_batch_ = nullptr;
+    std::vector<PatchJob>* patch_batch_ = nullptr;
+    const PatchCol* fused_patch_ = nullptr;  // decode_alp -> decode_bitpacked: patches K1w writes
+    std::vector<FsstChunk>* fsst_batch_ = nullptr;  // FSST chunks of a chunked string array
+    bool k1_fusable(const vxg_array& c) const;
+
+    vxg_status temp(uint64_t bytes, void** p) {
+        if (bytes == 0) bytes = 16;
+        if (plan_) {
+            VXG_TRY(hip_check(hipMalloc(p, (bytes + 15) & ~15ull), "hipMalloc (plan temporary)"));
+            plan_->allocs.push_back(*p);
+            return VXG_OK;
+        }
+        VXG_TRY(hip_check(hipMallocAsync(p, (bytes + 15) & ~15ull, s_), "hipMallocAsync"));
+        temps_.push_back(*p);
+        return VXG_OK;
+    }
+
+    static bool is_primitive_dtype(const vxg_array& a) { return a.dtype == VXG_DTYPE_PRIMITIVE; }
+    static int width(const vxg_array& a) { return ptype_width(a.ptype); }
+
+    const vxg_buffer* buf(const vxg_array& a, uint32_t i) const {
+        return i < a.n_buffers ? &a.buffers[i] : nullptr;
+    }
+    const vxg_array* child(const vxg_array& a, uint32_t i) const {
+        return i < a.n_children ? &a.children[i] : nullptr;
+    }
+
+    // Decode a primitive-typed array into dst (len * width bytes, 16-B aligned).
+    vxg_status decode_into(const vxg_array& a, void* dst);
+    // Canonical primitive values of `a` as a device pointer (aliases PRIMITIVE buffers).
+    vxg_status view_primitive(const vxg_array& a, const void** p);
+    vxg_status int_column(const vxg_array& a, IntCol& c);
+    // a patch-free 32/64-bit [FoR](BitPacked) integer column as a packed IntCol (*packed = true),
+    // validated; otherwise *packed = false and nothing is decoded
+    vxg_status packed_column(const vxg_array& a, IntCol& c, bool* packed);
+    vxg_status runend_column(const vxg_array& a, bool in_place, IntCol& c);
+
+    vxg_status decode_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs a, void* dst);
+    bool patch_fusable(const vxg_array& sparse, int value_width) const;
+    vxg_status sparse_patch_col(const vxg_array& sparse, PatchCol& pc);
+    vxg_status apply_sparse_patches(const vxg_array& sparse, int T, Epi epi, int vw, const UnpackArgs& a,
+                                    void* dst, uint64_t out_len);
+    vxg_status decode_alp(const vxg_array& a, void* dst);
+    vxg_status decode_dict_primitive(const vxg_array& a, void* dst);
+    vxg_status decode_chunked_primitive(const vxg_array& a, void* dst);
+    vxg_status decode_alprd(const vxg_array& a, void* dst);
+    vxg_status decode_sparse_values(const vxg_array& a, void* dst);
+
+    vxg_status take_values(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, void* dst);
+    vxg_status take_patches(const vxg_array& sp, TakePatches& p);
+    // A BitPacked-rooted cascade the fused compare kernel serves, validated (compare).
+    struct CmpFused {
+        const vxg_array* arr;    // the array or chunk
+        const vxg_array* bp;     // its BitPacked leaf
+        const vxg_array* outer;  // ALP patches, or null
+        int T, ck;
+        Epi epi;
+        EpiParams ep;
+        CmpChunk d;
+        bool excl;
+    };
+    vxg_status compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused);
+    vxg_status launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op);
+    // The string pieces of one row-compare target (the output bitmap, or the truth tables of the
+    // Dict pieces), by kernel.
+    struct StrRows {
+        std::vector<VbDictPiece> vbd;
+        std::vector<VbPiece> vb;
+        std::vector<ViewPiece> vw;
+        std::vector<FsstPiece> fs;
+    };
+    vxg_status compare_rows_of(const vxg_array& s, uint64_t out_bit, bool excl, bool table, StrRows& rows, bool* fell_back);
+    vxg_status launch_str_rows(StrRows& rows, const StrScalar& sc, void* out, int op, uint32_t& launches);
+    vxg_status validity_into(const vxg_array& a, void** bitmap);
+    // OR the values of a Bool-dtype array into the zeroed bit buffer `bits` at bit `off`.
+    vxg_status bools_into(const vxg_array& a, void* bits, uint64_t off);
+    vxg_status validity_source(const vxg_array& a, const vxg_array** node, int* kind);
+    vxg_status string_canonical(const vxg_array& a, vxg_canonical& out);
+    vxg_status string_lens(const vxg_array& a, std::vector<uint64_t>& lens,
+                           std::vector<std::pair<size_t, const vxg_array*>>& fsst) const;
+    vxg_status strings_into(const vxg_array& a, uint8_t* views, uint8_t* data, const vxg_data_buffer* bufs,
+                            uint32_t bidx, const uint8_t* validity);
+};
+
+}  // namespace vxg

@@ -1,0 +1,886 @@
+// planner_compute.hip — compute on compressed arrays: take (vortex-array/src/compute/take.rs:10-34,
+// take.hip), filter (compute/filter.rs:23-52, filter.hip), compare with a scalar
+// (compute/compare.rs:81-124, compare.hip) and compare of strings with a scalar (compare_str.hip).
+// Each reads the compressed tree where a kernel serves it and falls back to the canonical values.
+#include <algorithm>
+#include <cstring>
+#include <tuple>
+
+#include "filter.hpp"
+#include "planner.hpp"
+
+namespace vxg {
+
+// ---- compute::take on compressed arrays (vortex-array/src/compute/take.rs:10-34) ---------
+vxg_status Planner::take_patches(const vxg_array& sp, TakePatches& p) {
+    if (sp.encoding != VXG_ENC_SPARSE) return set_error(VXG_ERR_INVALID_ARGUMENT, "Can't patch with a non-Sparse array");
+    const vxg_array* idx = child(sp, 0);
+    const vxg_array* val = child(sp, 1);
+    if (!idx || !val || idx->len != val->len)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "Sparse patches need indices and values of equal length");
+    if (!ptype_is_int(idx->ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "Sparse indices must be integers");
+    VXG_TRY(view_primitive(*idx, &p.idx));
+    VXG_TRY(view_primitive(*val, &p.values));
+    p.n = idx->len;
+    p.off = sp.meta.sparse.indices_offset;
+    p.iw = width(*idx);
+    p.isg = ptype_is_signed(idx->ptype);
+    return VXG_OK;
+}
+
+vxg_status Planner::take_values(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, void* dst) {
+    if (n == 0) return VXG_OK;
+    auto via_canonical = [&]() -> vxg_status {  // canonicalize, then take the primitive
+        const void* pv;
+        VXG_TRY(view_primitive(a, &pv));
+        return launch_take(width(a), pv, a.len, iw, isg, idx, n, dst, ctx_->c.err_word, s_);
+    };
+    const vxg_array* bp = nullptr;
+    Epi epi = Epi::Plain;
+    EpiParams ep{};
+    TakePatches outer;
+    auto fl_child = [&](const vxg_array* c) -> const vxg_array* {  // FoR(BitPacked) or BitPacked
+        if (c && c->encoding == VXG_ENC_FL_FOR && child(*c, 0) && child(*c, 0)->encoding == VXG_ENC_FL_BITPACKED) {
+            ep.reference = c->meta.for_.reference;
+            ep.shift = c->meta.for_.shift;
+            return child(*c, 0);
+        }
+        return c && c->encoding == VXG_ENC_FL_BITPACKED ? c : nullptr;
+    };
+    switch (a.encoding) {
+    case VXG_ENC_FL_BITPACKED: bp = &a; break;  // bitpacking/compute/take.rs:21-125
+    case VXG_ENC_FL_FOR:                          // for/compute.rs:39-48: take the child, keep the FoR
+        bp = fl_child(&a);
+        epi = Epi::For;
+        break;
+    case VXG_ENC_ZIGZAG:  // zigzag/compute.rs: take the encoded child, decode
+        bp = fl_child(child(a, 0));
+        epi = Epi::ForZigZag;
+        break;
+    case VXG_ENC_ALP: {  // alp/compute.rs: take the encoded child and the patches
+        const bool f32 = a.ptype == VXG_F32;
+        const unsigned e = a.meta.alp.e, f = a.meta.alp.f;
+        if ((f32 && (e > 10 || f > 10)) || (!f32 && (a.ptype != VXG_F64 || e > 23 || f > 23))) return via_canonical();
+        bp = fl_child(child(a, 0));
+        epi = f32 ? Epi::AlpF32 : Epi::AlpF64;
+        ep.alp_a = f32 ? double(kF10f[f]) : kF10d[f];
+        ep.alp_b = f32 ? double(kIF10f[e]) : kIF10d[e];
+        if (bp && a.meta.alp.has_patches) {
+            if (!child(a, 1)) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: patches child missing");
+            VXG_TRY(take_patches(*child(a, 1), outer));
+        }
+        break;
+    }
+    case VXG_ENC_DICT: {  // dict/compute.rs:44-52: take the codes, then the values at them
+        const vxg_array* values = child(a, 0);
+        const vxg_array* codes = child(a, 1);
+        if (!values || !codes || values->dtype != VXG_DTYPE_PRIMITIVE || !ptype_is_int(codes->ptype))
+            return via_canonical();
+        void* tc;
+        VXG_TRY(temp(n * width(*codes), &tc));
+        VXG_TRY(take_values(*codes, idx, iw, isg, n, tc));
+        const void* pv;
+        VXG_TRY(view_primitive(*values, &pv));
+        return launch_take(width(*values), pv, values->len, width(*codes), false, tc, n, dst, ctx_->c.err_word, s_);
+    }
+    default: return via_canonical();
+    }
+    const int T = bp ? 8 * width(*bp) : 0;
+    const bool t_ok = bp && (epi == Epi::AlpF32 ? T == 32 : epi == Epi::AlpF64 ? T == 64 : T == 8 * width(a));
+    // bitpacking/compute/take.rs:23-31: many indices -> canonicalize and take the primitive
+    if (!t_ok || bp->len != a.len || n * 8 > a.len) return via_canonical();
+    const vxg_buffer* pb = buf(*bp, 0);
+    const unsigned W = bp->meta.bitpacked.bit_width, off = bp->meta.bitpacked.offset;
+    if (off > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
+    if (W > unsigned(T)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
+    const uint64_t nblk = (bp->len + off + 1023) / 1024, have = pb ? pb->len : 0;
+    if (W > 0 && have != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
+                                                       " packed bytes, got " + std::to_string(have));
+    TakePacked t{};
+    t.packed = pb ? static_cast<const uint8_t*>(pb->ptr) : nullptr;
+    t.W = W;
+    t.offset = off;
+    t.len = a.len;
+    t.idx = idx;
+    t.iw = iw;
+    t.isg = isg;
+    t.n = n;
+    t.out = dst;
+    t.ep = ep;
+    t.outer = outer;
+    t.err = ctx_->c.err_word;
+    if (bp->meta.bitpacked.has_patches) {  // take.rs:127-200: patches of the taken positions
+        if (!child(*bp, 0)) return set_error(VXG_ERR_INVALID_ARGUMENT, "BitPacked patches child missing");
+        VXG_TRY(take_patches(*child(*bp, 0), t.inner));
+    }
+    return launch_take_packed(T, epi, t, s_);
+}
+
+vxg_status Planner::take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out) {
+    if (a.dtype != VXG_DTYPE_PRIMITIVE) return set_error(VXG_ERR_NOT_IMPLEMENTED, "take supports primitive arrays");
+    out.kind = VXG_ENC_PRIMITIVE;
+    out.len = n;
+    out.dtype = a.dtype;
+    out.ptype = a.ptype;
+    out.values_bytes = n * width(a);
+    if (!out.values)
+        VXG_TRY(hip_check(hipMalloc(&out.values, out.values_bytes ? out.values_bytes : 16), "take values alloc"));
+    VXG_TRY(take_values(a, idx, iw, isg, n, out.values));
+    const vxg_array* node;
+    int kind;
+    VXG_TRY(validity_source(a, &node, &kind));
+    if (kind == 0) {  // validity.take of NonNullable / AllValid: no nulls
+        out.validity = nullptr;
+        return VXG_OK;
+    }
+    void* src = nullptr;  // the array's validity, then taken at the indices
+    VXG_TRY(temp(((a.len + 31) / 32) * 4, &src));
+    VXG_TRY(validity_into(a, &src));
+    const uint64_t bytes = ((n + 31) / 32) * 4;
+    if (!out.validity) VXG_TRY(hip_check(hipMalloc(&out.validity, bytes ? bytes : 4), "take validity alloc"));
+    return launch_gather_bits(out.validity, idx, iw, isg, n, static_cast<const uint8_t*>(src), a.len, ctx_->c.err_word,
+                              s_);
+}
+
+// ---- compute::compare with a scalar (vortex-array/src/compute/compare.rs:81-124) ----------
+// Is `a` a cascade the fused kernel serves -- BitPacked, FoR(BitPacked), ZigZag or ALP over
+// either?  Then validate its packed buffer exactly like take_values and describe it.
+vxg_status Planner::compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused) {
+    *fused = false;
+    f = CmpFused{};
+    f.arr = &a;
+    f.epi = Epi::Plain;
+    f.ck = ptype_is_signed(a.ptype) ? kCmpSigned : kCmpUnsigned;
+    auto fl_child = [&](const vxg_array* c) -> const vxg_array* {  // FoR(BitPacked) or BitPacked
+        if (c && c->encoding == VXG_ENC_FL_FOR && child(*c, 0) && child(*c, 0)->encoding == VXG_ENC_FL_BITPACKED) {
+            f.ep.reference = c->meta.for_.reference;
+            f.ep.shift = c->meta.for_.shift;
+            return child(*c, 0);
+        }
+        return c && c->encoding == VXG_ENC_FL_BITPACKED ? c : nullptr;
+    };
+    switch (a.encoding) {
+    case VXG_ENC_FL_BITPACKED: f.bp = &a; break;
+    case VXG_ENC_FL_FOR:
+        f.bp = fl_child(&a);
+        f.epi = Epi::For;
+        break;
+    case VXG_ENC_ZIGZAG:
+        if (!ptype_is_signed(a.ptype)) return VXG_OK;  // the fallback reports it
+        f.bp = fl_child(child(a, 0));
+        f.epi = Epi::ForZigZag;
+        break;
+    case VXG_ENC_ALP: {
+        const bool f32 = a.ptype == VXG_F32;
+        const unsigned e = a.meta.alp.e, fx = a.meta.alp.f;
+        if ((f32 && (e > 10 || fx > 10)) || (!f32 && (a.ptype != VXG_F64 || e > 23 || fx > 23))) return VXG_OK;
+        f.bp = fl_child(child(a, 0));
+        f.epi = f32 ? Epi::AlpF32 : Epi::AlpF64;
+        f.ck = kCmpFloat;
+        f.ep.alp_a = f32 ? double(kF10f[fx]) : kF10d[fx];
+        f.ep.alp_b = f32 ? double(kIF10f[e]) : kIF10d[e];
+        if (f.bp && a.meta.alp.has_patches) {
+            if (!child(a, 1)) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: patches child missing");
+            f.outer = child(a, 1);
+        }
+        break;
+    }
+    default: return VXG_OK;
+    }
+    if (!f.bp || !ptype_is_int(f.bp->ptype) || !(ptype_is_int(a.ptype) || f.ck == kCmpFloat)) return VXG_OK;
+    f.T = 8 * width(*f.bp);
+    if (f.T != 8 * width(a) || f.bp->len != a.len) return VXG_OK;
+    const vxg_buffer* pb = buf(*f.bp, 0);
+    const unsigned W = f.bp->meta.bitpacked.bit_width, off = f.bp->meta.bitpacked.offset;
+    if (off > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
+    if (W > unsigned(f.T)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
+    const uint64_t nblk = (a.len + off + 1023) / 1024, have = pb ? pb->len : 0;
+    if (W > 0 && have != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
+                                                       " packed bytes, got " + std::to_string(have));
+    if (W > 0 && (reinterpret_cast<uintptr_t>(pb->ptr) & 15))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "packed buffer must be 16-byte aligned");
+    if (a.len > kCmpMaxLen) return set_error(VXG_ERR_INVALID_ARGUMENT, "array too long for one compare launch");
+    // patch children are checked here, before the caller allocates or launches anything
+    auto patch_values = [&](const vxg_array& sp) -> const vxg_array* {
+        return sp.encoding == VXG_ENC_SPARSE && child(sp, 0) && child(sp, 1) ? child(sp, 1) : nullptr;
+    };
+    if (f.bp->meta.bitpacked.has_patches) {
+        if (!child(*f.bp, 0)) return set_error(VXG_ERR_INVALID_ARGUMENT, "BitPacked patches child missing");
+        const vxg_array* pv = patch_values(*child(*f.bp, 0));
+        if (pv && width(*pv) != f.T / 8)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "BitPacked patch values must have the array's width");
+    }
+    if (f.outer) {
+        const vxg_array* pv = patch_values(*f.outer);
+        if (pv && pv->ptype != a.ptype)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "ALP patch values must have the array's ptype");
+    }
+    f.ep.err = ctx_->c.err_word;
+    f.d.packed = pb ? static_cast<const uint8_t*>(pb->ptr) : nullptr;
+    f.d.len_lo = uint32_t(a.len);
+    f.d.len_hi = uint8_t(a.len >> 32);
+    f.d.out_bit = out_bit;
+    f.d.reference = f.ep.reference;
+    f.d.alp_e = a.encoding == VXG_ENC_ALP ? a.meta.alp.e : 0;
+    f.d.alp_f = a.encoding == VXG_ENC_ALP ? a.meta.alp.f : 0;
+    f.d.offset = uint16_t(off);
+    f.d.shift = uint8_t(f.ep.shift);
+    f.d.W = uint8_t(W);
+    *fused = true;
+    return VXG_OK;
+}
+
+// The chunks of one kernel instantiation (T, epilogue, compared type; at most kCmpArgChunks) in one
+// launch: the table is the kernel argument -- nothing is uploaded and no host state outlives the call.
+vxg_status Planner::launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op) {
+    uint64_t blocks = 0;
+    for (const CmpFused* f : group) blocks += f->d.n_blocks();
+    // small launches take fewer blocks per workgroup (>= 4: one per wave), like K1w's rule
+    uint32_t pick = uint32_t(std::min<uint64_t>(32, blocks / 1024)) & ~3u;
+    if (pick < 4) pick = 4;
+    CmpTable tab{};
+    uint64_t groups = 0;
+    uint32_t lds = 0;
+    for (const CmpFused* f : group) {
+        CmpChunk& c = tab.c[tab.n++];
+        c = f->d;
+        const uint32_t bpw = std::min(cmp_bpw_max(c.W), pick);
+        c.bpw_excl = uint8_t(bpw | (f->excl ? 0x80u : 0u));
+        c.first_group = uint32_t(groups);
+        groups += (c.n_blocks() + bpw - 1) / bpw;
+        lds = std::max(lds, bpw * 128u * c.W);
+    }
+    if (groups == 0) groups = 1;  // an empty array: one workgroup that finds no block
+    const CmpFused& f0 = *group[0];
+    // (+ one word row of slack: a value's second word is read unconditionally)
+    return launch_cmp_packed(f0.T, f0.epi, f0.ck, tab, groups, lds + 128, out, scalar_bits, op, s_);
+}
+
+vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
+                            vxg_compare_info& info) {
+    if (a.dtype != VXG_DTYPE_PRIMITIVE) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare supports primitive arrays");
+    if (width(a) == 0 || a.ptype == VXG_F16) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare does not support f16");
+    if (op < VXG_CMP_EQ || op > VXG_CMP_LTE)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare operator " + std::to_string(op));
+    if (flags & ~uint32_t(VXG_CMP_NULL_AS_FALSE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare flags");
+    const uint64_t n = a.len, words = (n + 63) / 64, bytes = words * 8;
+
+    // the pieces: the array itself, or the chunks of a top-level ChunkedArray at their bit offsets
+    std::vector<std::pair<const vxg_array*, uint64_t>> pieces;
+    if (a.encoding == VXG_ENC_CHUNKED) {
+        if (a.n_children != a.meta.chunked.nchunks + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked child count != nchunks + 1");
+        uint64_t off = 0;
+        for (uint32_t i = 1; i < a.n_children; i++) {
+            const vxg_array& c = a.children[i];
+            if (c.dtype != a.dtype || c.ptype != a.ptype)
+                return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the same dtype");
+            pieces.emplace_back(&c, off);
+            off += c.len;
+        }
+        if (off != n) return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked chunk lengths do not sum to len");
+    } else {
+        pieces.emplace_back(&a, 0);
+    }
+    // classify and validate every piece before anything is allocated or launched
+    std::vector<CmpFused> fused;
+    std::vector<std::pair<const vxg_array*, uint64_t>> plain;
+    fused.reserve(pieces.size());
+    bool zero = false;  // some word is ORed in: the bitmap starts zeroed
+    auto word_edges = [&](uint64_t ob, uint64_t len) { return ob % 64 == 0 && ((ob + len) % 64 == 0 || ob + len == n); };
+    for (const auto& [p, ob] : pieces) {
+        CmpFused f;
+        bool is_fused;
+        VXG_TRY(compare_shape(*p, ob, f, &is_fused));
+        if (is_fused) {
+            f.excl = word_edges(ob, p->len) && f.d.offset % 64 == 0;
+            if (p->len == 0 && p != &a) {  // an empty chunk: counted, nothing to launch
+                info.fused_chunks++;
+                continue;
+            }
+            zero = zero || (p->len && !f.excl);
+            fused.push_back(f);
+        } else {
+            zero = zero || (p->len && !word_edges(ob, p->len));
+            plain.emplace_back(p, ob);
+        }
+    }
+
+    out.kind = VXG_ENC_BOOL;
+    out.len = n;
+    out.dtype = VXG_DTYPE_BOOL;
+    out.ptype = VXG_U8;
+    out.values_bytes = bytes;
+    if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, bytes ? bytes : 8), "compare values alloc"));
+    if (reinterpret_cast<uintptr_t>(out.values) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare output must be 8-byte aligned");
+    if (zero) VXG_TRY(launch_copy_bytes(out.values, nullptr, bytes, s_));
+
+    // fused launches, one per kernel instantiation
+    std::vector<CmpFused*> order;
+    for (CmpFused& f : fused) order.push_back(&f);
+    std::stable_sort(order.begin(), order.end(), [](const CmpFused* x, const CmpFused* y) {
+        return std::make_tuple(x->T, int(x->epi), x->ck) < std::make_tuple(y->T, int(y->epi), y->ck);
+    });
+    for (size_t i = 0; i < order.size();) {
+        size_t j = i;
+        while (j < order.size() && j - i < size_t(kCmpArgChunks) && order[j]->T == order[i]->T &&
+               order[j]->epi == order[i]->epi && order[j]->ck == order[i]->ck)
+            j++;
+        std::vector<CmpFused*> group(order.begin() + i, order.begin() + j);
+        VXG_TRY(launch_compare_group(group, out.values, scalar_bits, op));
+        info.fused_launches++;
+        info.fused_chunks += uint32_t(j - i);
+        i = j;
+    }
+    // patched rows are compared again: BitPacked's raw values through the epilogue, then ALP's
+    for (const CmpFused& f : fused) {
+        if (f.bp->meta.bitpacked.has_patches) {
+            TakePatches tp;
+            VXG_TRY(take_patches(*child(*f.bp, 0), tp));
+            VXG_TRY(launch_cmp_patch(f.T, f.epi, f.ck, tp, f.d.len(), out.values, f.d.out_bit, f.ep, scalar_bits, op, s_));
+            info.patch_launches += tp.n != 0;
+        }
+        if (f.outer) {
+            TakePatches tp;
+            VXG_TRY(take_patches(*f.outer, tp));
+            VXG_TRY(launch_cmp_patch_raw(a.ptype, tp, f.d.len(), out.values, f.d.out_bit, scalar_bits, op, ctx_->c.err_word,
+                                         s_));
+            info.patch_launches += tp.n != 0;
+        }
+    }
+    // every other encoding: the canonical values (a Primitive array in place), then the plain kernel
+    for (const auto& [p, ob] : plain) {
+        const void* pv;
+        VXG_TRY(view_primitive(*p, &pv));
+        if (reinterpret_cast<uintptr_t>(pv) % uint64_t(width(a)))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "primitive buffer must be aligned to the value width");
+        VXG_TRY(launch_cmp_plain(a.ptype, pv, p->len, out.values, ob, scalar_bits, op, word_edges(ob, p->len), s_));
+        info.fallback_arrays++;
+    }
+
+    // value bits of null rows are 0; null_as_false drops the validity (filtering.rs:42)
+    const vxg_array* vnode;
+    int vkind;
+    VXG_TRY(validity_source(a, &vnode, &vkind));
+    const bool null_as_false = (flags & VXG_CMP_NULL_AS_FALSE) != 0;
+    if (vkind == 0) {
+        out.validity = nullptr;
+        return VXG_OK;
+    }
+    void* vbits = nullptr;
+    if (null_as_false) VXG_TRY(temp(bytes, &vbits));
+    else if (out.validity) vbits = out.validity;
+    else {
+        VXG_TRY(hip_check(hipMalloc(&vbits, bytes ? bytes : 8), "compare validity alloc"));
+        out.validity = vbits;  // (the entry point releases it if a later step fails)
+    }
+    if (reinterpret_cast<uintptr_t>(vbits) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare validity must be 8-byte aligned");
+    if (n) {  // (an empty array's bitmaps hold no bytes: nothing is written)
+        VXG_TRY(launch_copy_bytes(vbits, nullptr, bytes, s_));
+        VXG_TRY(validity_into(a, &vbits));
+        VXG_TRY(launch_and_words(out.values, vbits, words, s_));
+    }
+    out.validity = null_as_false ? nullptr : vbits;
+    return VXG_OK;
+}
+
+// ---- compute::compare of strings with a scalar (compare_str.hip) ---------------------------
+// The rows of string array `s` (a piece, or the values of a Dict piece) as a piece of the row
+// kernels, at bit out_bit of their target.  VarBin, VarBinView and FSST are read where they lie;
+// anything else is canonicalized into temporaries and compared as a VarBinView (*fell_back).
+// `table`: the target is a truth table (out_bit on a word, every word exclusive), so a VarBin
+// with plain offsets takes the 40-byte form.
+vxg_status Planner::compare_rows_of(const vxg_array& s, uint64_t out_bit, bool excl, bool table, StrRows& rows,
+                                    bool* fell_back) {
+    *fell_back = false;
+    if (!is_string(s)) return set_error(VXG_ERR_MISMATCHED_TYPES, "compare: expected a utf8 or binary array");
+    if (s.len == 0) return VXG_OK;
+    auto bytes_of = [&](const vxg_array& b, const void** p) -> vxg_status {
+        if (b.dtype != VXG_DTYPE_PRIMITIVE || width(b) != 1)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "string bytes must be a u8 array");
+        return view_primitive(b, p);
+    };
+    auto view_piece = [&](const void* views, const std::vector<StrBuf>& bufs) -> vxg_status {
+        if (reinterpret_cast<uintptr_t>(views) & 15)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views must be 16-byte aligned");
+        ViewPiece p{};
+        p.views = static_cast<const uint8_t*>(views);
+        p.n_buffers = uint32_t(bufs.size());
+        if (bufs.size() == 1) p.buf0 = bufs[0];
+        if (bufs.size() > 1) {  // a device table of the buffers, like Planner::filter's
+            void* d;
+            VXG_TRY(temp(bufs.size() * sizeof(StrBuf), &d));
+            VXG_TRY(hip_check(hipMemcpyAsync(d, bufs.data(), bufs.size() * sizeof(StrBuf), hipMemcpyHostToDevice, s_),
+                              "compare buffer table upload"));
+            VXG_TRY(hip_check(hipStreamSynchronize(s_), "compare buffer table sync"));  // `bufs` is read by the upload
+            p.bufs = static_cast<const StrBuf*>(d);
+        }
+        p.out_bit = out_bit;
+        p.n = s.len;
+        p.excl = excl;
+        rows.vw.push_back(p);
+        return VXG_OK;
+    };
+    switch (s.encoding) {
+    case VXG_ENC_VARBIN: {
+        const vxg_array* offs = child(s, 0);
+        const vxg_array* bytes = child(s, 1);
+        if (!offs || !bytes) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinArray needs offsets and bytes");
+        if (!ptype_is_int(offs->ptype) || offs->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "VarBin offsets must be integers");
+        if (offs->len < s.len + 1) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets shorter than len + 1");
+        const void* pb;
+        VXG_TRY(bytes_of(*bytes, &pb));
+        if (table && offs->encoding == VXG_ENC_PRIMITIVE && bytes->len <= 0xFFFFFFFFull && s.len <= 0xFFFFFFFFull &&
+            out_bit % 64 == 0 && out_bit / 64 <= 0xFFFFFFFFull) {
+            const void* po;
+            VXG_TRY(view_primitive(*offs, &po));
+            if (reinterpret_cast<uintptr_t>(po) % uint64_t(width(*offs)))
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets must be aligned to their width");
+            VbDictPiece p{};
+            p.bytes = static_cast<const uint8_t*>(pb);
+            p.offs = po;
+            p.bytes_len = uint32_t(bytes->len);
+            p.out_word = uint32_t(out_bit / 64);
+            p.n = uint32_t(s.len);
+            p.width = uint8_t(width(*offs));
+            p.sgn = ptype_is_signed(offs->ptype);
+            rows.vbd.push_back(p);
+            return VXG_OK;
+        }
+        IntCol oc;
+        VXG_TRY(int_column(*offs, oc));
+        if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets must be aligned to their width");
+        VbPiece p{};
+        p.bytes = static_cast<const uint8_t*>(pb);
+        p.bytes_len = bytes->len;
+        p.offs = to_ccol(oc);
+        p.out_bit = out_bit;
+        p.n = s.len;
+        p.excl = excl;
+        rows.vb.push_back(p);
+        return VXG_OK;
+    }
+    case VXG_ENC_VARBINVIEW: {
+        const vxg_array* vw = child(s, 0);
+        const uint32_t nb = s.meta.varbinview.n_buffers;
+        if (!vw || s.n_children < 1 + nb)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinViewArray: missing views/data buffers");
+        const void* pv;
+        VXG_TRY(bytes_of(*vw, &pv));
+        if (vw->len < 16 * s.len) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views shorter than 16 * len");
+        std::vector<StrBuf> bufs(nb);
+        for (uint32_t b = 0; b < nb; b++) {
+            const void* pb;
+            VXG_TRY(bytes_of(s.children[1 + b], &pb));
+            bufs[b] = StrBuf{static_cast<const uint8_t*>(pb), s.children[1 + b].len};
+        }
+        return view_piece(pv, bufs);
+    }
+    case VXG_ENC_FSST: {
+        const vxg_array* sym = child(s, 0);
+        const vxg_array* slen = child(s, 1);
+        const vxg_array* codes = child(s, 2);
+        const vxg_array* ulen = child(s, 3);
+        if (!sym || !slen || !codes || !ulen || codes->encoding != VXG_ENC_VARBIN || !child(*codes, 0) || !child(*codes, 1))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSSTArray needs symbols, lengths, VarBin codes, lengths");
+        if (sym->len > 255 || slen->len < sym->len || width(*sym) != 8 || width(*slen) != 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbol table must hold at most 255 u64 symbols and their u8 lengths");
+        if (codes->len != s.len || ulen->len < s.len || child(*codes, 0)->len < s.len + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST codes / lengths do not cover the array");
+        if (!ptype_is_int(child(*codes, 0)->ptype) || !ptype_is_int(ulen->ptype))
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "FSST offsets and lengths must be integers");
+        const void *psym, *pslen, *pcb;
+        VXG_TRY(view_primitive(*sym, &psym));
+        VXG_TRY(view_primitive(*slen, &pslen));
+        VXG_TRY(bytes_of(*child(*codes, 1), &pcb));
+        if (reinterpret_cast<uintptr_t>(psym) & 7) return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbols must be 8-byte aligned");
+        IntCol oc, lc;
+        VXG_TRY(int_column(*child(*codes, 0), oc));
+        VXG_TRY(int_column(*ulen, lc));
+        if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width) ||
+            reinterpret_cast<uintptr_t>(lc.p) % uint64_t(lc.packed ? 16 : lc.width))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST offsets / lengths must be aligned to their width");
+        FsstPiece p{};
+        p.symbols = static_cast<const uint64_t*>(psym);
+        p.sym_lens = static_cast<const uint8_t*>(pslen);
+        p.codes = static_cast<const uint8_t*>(pcb);
+        p.codes_len = child(*codes, 1)->len;
+        p.offs = to_ccol(oc);
+        p.lens = to_ccol(lc);
+        p.out_bit = out_bit;
+        p.n = s.len;
+        p.excl = excl;
+        p.n_symbols = uint32_t(sym->len);
+        rows.fs.push_back(p);
+        return VXG_OK;
+    }
+    default: {
+        // canonical views + data in temporaries (as Planner::filter builds its source)
+        *fell_back = true;
+        vxg_canonical src{};
+        std::vector<vxg_data_buffer> lay;
+        uint64_t extent;
+        VXG_TRY(string_layout(s, lay, extent));
+        const vxg_array* vnode;
+        int vkind;
+        VXG_TRY(validity_source(s, &vnode, &vkind));
+        if (vkind != 0) VXG_TRY(temp(((s.len + 31) / 32) * 4, &src.validity));
+        VXG_TRY(temp(16 * s.len, &src.views));
+        VXG_TRY(temp(extent + 16, &src.data));
+        src.data_bytes = extent;
+        src.data_buffers = lay.data();
+        src.n_data_buffers = src.data_buffers_cap = uint32_t(lay.size());
+        VXG_TRY(string_canonical(s, src));
+        std::vector<StrBuf> bufs(lay.size());
+        for (size_t b = 0; b < lay.size(); b++)
+            bufs[b] = StrBuf{static_cast<const uint8_t*>(src.data) + lay[b].offset, lay[b].len};
+        return view_piece(src.views, bufs);
+    }
+    }
+}
+
+// Every piece of `rows` into `out`: one launch per kind and per kernel-argument table.
+vxg_status Planner::launch_str_rows(StrRows& rows, const StrScalar& sc, void* out, int op, uint32_t& launches) {
+    uint32_t* err = ctx_->c.err_word;
+    auto run = [&](auto& v, auto tab, auto groups_of, auto launch) -> vxg_status {
+        constexpr size_t cap = sizeof(tab.c) / sizeof(tab.c[0]);
+        for (size_t i = 0; i < v.size(); i += cap) {
+            tab.n = 0;
+            uint64_t groups = 0;
+            for (size_t k = i; k < v.size() && k < i + cap; k++) {
+                v[k].first_group = uint32_t(groups);
+                groups += groups_of(v[k]);
+                tab.c[tab.n++] = v[k];
+            }
+            VXG_TRY(launch(tab, groups));
+            launches++;
+        }
+        return VXG_OK;
+    };
+    VXG_TRY(run(rows.vbd, VbDictTab{}, [](const VbDictPiece& p) { return piece_groups(0, p.n); },
+                [&](const VbDictTab& t, uint64_t g) { return launch_cmpb_varbin_dict(t, g, sc, out, err, op, s_); }));
+    VXG_TRY(run(rows.vb, VbTab{}, [](const VbPiece& p) { return piece_groups(p.out_bit, p.n); },
+                [&](const VbTab& t, uint64_t g) { return launch_cmpb_varbin(t, g, sc, out, err, op, s_); }));
+    VXG_TRY(run(rows.vw, ViewTab{}, [](const ViewPiece& p) { return piece_groups(p.out_bit, p.n); },
+                [&](const ViewTab& t, uint64_t g) { return launch_cmpb_views(t, g, sc, out, err, op, s_); }));
+    VXG_TRY(run(rows.fs, FsstTab{}, [](const FsstPiece& p) { return piece_groups(p.out_bit, p.n); },
+                [&](const FsstTab& t, uint64_t g) { return launch_cmpb_fsst(t, g, sc, out, err, op, s_); }));
+    return VXG_OK;
+}
+
+vxg_status Planner::compare_bytes(const vxg_array& a, int op, const void* scalar_host, uint64_t scalar_len, uint32_t flags,
+                                  vxg_canonical& out, vxg_compare_bytes_info& info) {
+    if (!is_string(a)) return set_error(VXG_ERR_MISMATCHED_TYPES, "compare_bytes needs a utf8 or binary array");
+    if (op < VXG_CMP_EQ || op > VXG_CMP_LTE)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare operator " + std::to_string(op));
+    if (flags & ~uint32_t(VXG_CMP_NULL_AS_FALSE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare flags");
+    if (a.len > kCmpMaxLen) return set_error(VXG_ERR_INVALID_ARGUMENT, "array too long for one compare launch");
+    const uint64_t n = a.len, words = (n + 63) / 64, bytes = words * 8;
+
+    // the pieces: the array itself, or the chunks of a top-level ChunkedArray at their bit offsets
+    std::vector<std::pair<const vxg_array*, uint64_t>> pieces;
+    if (a.encoding == VXG_ENC_CHUNKED) {
+        if (a.n_children != a.meta.chunked.nchunks + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked child count != nchunks + 1");
+        uint64_t off = 0;
+        for (uint32_t i = 1; i < a.n_children; i++) {
+            const vxg_array& c = a.children[i];
+            if (c.dtype != a.dtype) return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the same dtype");
+            pieces.emplace_back(&c, off);
+            off += c.len;
+        }
+        if (off != n) return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked chunk lengths do not sum to len");
+    } else {
+        pieces.emplace_back(&a, 0);
+    }
+
+    // classify and validate every piece before the output is allocated or a compare is launched
+    struct DictPacked {
+        int T;
+        CmpChunk d;
+        bool excl;
+    };
+    StrRows table_rows, out_rows;
+    std::vector<DictPacked> packed;
+    std::vector<DictPlainPiece> plain;
+    uint64_t tt_words = 0;
+    bool zero = false;  // some word is ORed in: the bitmap starts zeroed
+    auto word_edges = [&](uint64_t ob, uint64_t len) { return ob % 64 == 0 && ((ob + len) % 64 == 0 || ob + len == n); };
+    for (const auto& [p, ob] : pieces) {
+        const bool edges = word_edges(ob, p->len);
+        bool fell = false;
+        if (p->encoding != VXG_ENC_DICT) {
+            VXG_TRY(compare_rows_of(*p, ob, edges, false, out_rows, &fell));
+            if (fell) info.fallback_arrays++;
+            else info.direct_chunks++;
+            zero = zero || (p->len && !edges);
+            continue;
+        }
+        const vxg_array* values = child(*p, 0);
+        const vxg_array* codes = child(*p, 1);
+        if (!values || !codes) return set_error(VXG_ERR_INVALID_ARGUMENT, "DictArray needs values and codes");
+        if (!ptype_is_int(codes->ptype) || codes->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "Dict codes must be integers");
+        if (codes->len != p->len) return set_error(VXG_ERR_INVALID_ARGUMENT, "Dict codes length != array length");
+        if (values->len > 0xFFFFFFFFull) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare: dictionary of 2^32 or more values");
+        info.dict_chunks++;
+        if (p->len == 0) continue;  // an empty chunk: counted, nothing to launch
+        const uint64_t tword = tt_words;
+        if (tword > 0xFFFFFFFFull) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare: truth tables exceed 2^32 words");
+        tt_words += std::max<uint64_t>(1, (values->len + 63) / 64);
+        // (a) the truth table: the dictionary's values, compared like any string array
+        VXG_TRY(compare_rows_of(*values, tword * 64, true, true, table_rows, &fell));
+        if (fell) info.fallback_arrays++;
+        // (b) the lookup
+        const int T = 8 * width(*codes);
+        if (codes->encoding == VXG_ENC_FL_BITPACKED && ptype_is_unsigned(codes->ptype) && !codes->meta.bitpacked.has_patches) {
+            const vxg_buffer* pb = buf(*codes, 0);
+            const unsigned W = codes->meta.bitpacked.bit_width, off = codes->meta.bitpacked.offset;
+            if (off > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
+            if (W > unsigned(T)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
+            const uint64_t nblk = (p->len + off + 1023) / 1024, have = pb ? pb->len : 0;
+            if (W > 0 && have != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
+                                                               " packed bytes, got " + std::to_string(have));
+            if (W > 0 && (reinterpret_cast<uintptr_t>(pb->ptr) & 15))
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "packed buffer must be 16-byte aligned");
+            DictPacked dp{};
+            dp.T = T;
+            dp.d.packed = pb ? static_cast<const uint8_t*>(pb->ptr) : nullptr;
+            dp.d.reference = tword | uint64_t(values->len) << 32;
+            dp.d.out_bit = ob;
+            dp.d.len_lo = uint32_t(p->len);
+            dp.d.len_hi = uint8_t(p->len >> 32);
+            dp.d.offset = uint16_t(off);
+            dp.d.W = uint8_t(W);
+            dp.excl = edges && off % 64 == 0;
+            zero = zero || !dp.excl;
+            packed.push_back(dp);
+        } else {  // a Primitive array in place; any other encoding through a temporary
+            const void* pc;
+            VXG_TRY(view_primitive(*codes, &pc));
+            if (reinterpret_cast<uintptr_t>(pc) % uint64_t(width(*codes)))
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "primitive buffer must be aligned to the value width");
+            DictPlainPiece d{};
+            d.codes = pc;
+            d.out_bit = ob;
+            d.n = p->len;
+            d.tword = uint32_t(tword);
+            d.vlen = uint32_t(values->len);
+            d.width = uint8_t(width(*codes));
+            d.sgn = ptype_is_signed(codes->ptype);
+            d.excl = edges;
+            zero = zero || !edges;
+            plain.push_back(d);
+        }
+    }
+
+    // the scalar: short ones ride in the kernel argument, long ones go to a temporary
+    StrScalar sc{};
+    sc.len = scalar_len;
+    if (scalar_len <= kStrInline) {
+        if (scalar_len) std::memcpy(sc.inl, scalar_host, size_t(scalar_len));
+    } else {
+        void* d;
+        VXG_TRY(temp(scalar_len, &d));
+        VXG_TRY(hip_check(hipMemcpyAsync(d, scalar_host, scalar_len, hipMemcpyHostToDevice, s_), "compare scalar upload"));
+        VXG_TRY(hip_check(hipStreamSynchronize(s_), "compare scalar sync"));  // the caller may free its bytes
+        sc.dev = static_cast<const uint8_t*>(d);
+    }
+
+    out.kind = VXG_ENC_BOOL;
+    out.len = n;
+    out.dtype = VXG_DTYPE_BOOL;
+    out.ptype = VXG_U8;
+    out.values_bytes = bytes;
+    if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, bytes ? bytes : 8), "compare values alloc"));
+    if (reinterpret_cast<uintptr_t>(out.values) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare output must be 8-byte aligned");
+    if (zero) VXG_TRY(launch_copy_bytes(out.values, nullptr, bytes, s_));
+
+    // truth tables: every dictionary starts on a 64-bit word of one temporary
+    void* tt = nullptr;
+    if (tt_words) {
+        VXG_TRY(temp(tt_words * 8, &tt));
+        VXG_TRY(launch_str_rows(table_rows, sc, tt, op, info.table_launches));
+    }
+    // lookups of the BitPacked codes, one launch per code width T
+    std::stable_sort(packed.begin(), packed.end(), [](const DictPacked& x, const DictPacked& y) { return x.T < y.T; });
+    for (size_t i = 0; i < packed.size();) {
+        size_t j = i;
+        uint64_t blocks = 0;
+        while (j < packed.size() && j - i < size_t(kCmpArgChunks) && packed[j].T == packed[i].T) blocks += packed[j++].d.n_blocks();
+        uint32_t pick = uint32_t(std::min<uint64_t>(32, blocks / 1024)) & ~3u;  // launch_compare_group's rule
+        if (pick < 4) pick = 4;
+        CmpTable tab{};
+        uint64_t groups = 0;
+        uint32_t lds = 0;
+        for (size_t k = i; k < j; k++) {
+            CmpChunk& c = tab.c[tab.n++];
+            c = packed[k].d;
+            const uint32_t bpw = std::min(cmp_bpw_max(c.W), pick);
+            c.bpw_excl = uint8_t(bpw | (packed[k].excl ? 0x80u : 0u));
+            c.first_group = uint32_t(groups);
+            groups += (c.n_blocks() + bpw - 1) / bpw;
+            lds = std::max(lds, bpw * 128u * c.W);
+        }
+        VXG_TRY(launch_cmpb_dict_packed(packed[i].T, tab, groups, lds + 128, out.values, tt, ctx_->c.err_word, s_));
+        info.dict_launches++;
+        i = j;
+    }
+    for (size_t i = 0; i < plain.size(); i += size_t(kStrArgPieces40)) {
+        DictPlainTab tab{};
+        uint64_t groups = 0;
+        for (size_t k = i; k < plain.size() && k < i + size_t(kStrArgPieces40); k++) {
+            plain[k].first_group = uint32_t(groups);
+            groups += piece_groups(plain[k].out_bit, plain[k].n);
+            tab.c[tab.n++] = plain[k];
+        }
+        VXG_TRY(launch_cmpb_dict_plain(tab, groups, out.values, tt, ctx_->c.err_word, s_));
+        info.dict_launches++;
+    }
+    // VarBin / VarBinView / FSST pieces in place, and the canonicalized ones
+    VXG_TRY(launch_str_rows(out_rows, sc, out.values, op, info.direct_launches));
+
+    // value bits of null rows are 0; null_as_false drops the validity (filtering.rs:42)
+    const vxg_array* vnode;
+    int vkind;
+    VXG_TRY(validity_source(a, &vnode, &vkind));
+    const bool null_as_false = (flags & VXG_CMP_NULL_AS_FALSE) != 0;
+    if (vkind == 0) {
+        out.validity = nullptr;
+        return VXG_OK;
+    }
+    void* vbits = nullptr;
+    if (null_as_false) VXG_TRY(temp(bytes, &vbits));
+    else if (out.validity) vbits = out.validity;
+    else {
+        VXG_TRY(hip_check(hipMalloc(&vbits, bytes ? bytes : 8), "compare validity alloc"));
+        out.validity = vbits;  // (the entry point releases it if a later step fails)
+    }
+    if (reinterpret_cast<uintptr_t>(vbits) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "compare validity must be 8-byte aligned");
+    if (n) {  // (an empty array's bitmaps hold no bytes: nothing is written)
+        VXG_TRY(launch_copy_bytes(vbits, nullptr, bytes, s_));
+        VXG_TRY(validity_into(a, &vbits));
+        VXG_TRY(launch_and_words(out.values, vbits, words, s_));
+    }
+    out.validity = null_as_false ? nullptr : vbits;
+    return VXG_OK;
+}
+
+// compute::filter (compute/filter.rs:23-52).  The predicate (any Bool encoding) becomes a bit
+// buffer padded to whole u64 words; one sync reads the true count (the filtered length the
+// reference's Array carries); the array is canonicalized into temporaries and compacted.
+// Strings get a new single heap of the selected rows' bytes (VarBin/FSST filter, then
+// varbin/flatten.rs), null rows as empty values.
+vxg_status Planner::filter(const vxg_array& a, const vxg_array& pred, vxg_canonical& out) {
+    if (pred.dtype != VXG_DTYPE_BOOL || pred.nullable)  // filter.rs:27-32
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "predicate must be non-nullable bool");
+    if (pred.len != a.len)  // filter.rs:33-39
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "predicate.len() is " + std::to_string(pred.len) +
+                                                       ", does not equal array.len() of " + std::to_string(a.len));
+    const bool is_str = is_string(a);
+    if (!is_str && a.dtype != VXG_DTYPE_BOOL && a.dtype != VXG_DTYPE_PRIMITIVE)
+        return set_error(VXG_ERR_NOT_IMPLEMENTED, "filter supports primitive, bool and utf8/binary dtypes");
+    const uint64_t n = a.len, tiles = filter_tiles(n);
+    void* mask;
+    VXG_TRY(temp(((n + 63) / 64) * 8, &mask));
+    VXG_TRY(launch_copy_bytes(mask, nullptr, ((n + 63) / 64) * 8, s_));
+    VXG_TRY(bools_into(pred, mask, 0));
+    void* toff;
+    VXG_TRY(temp((tiles + 1) * 8, &toff));
+    const uint64_t* m = static_cast<const uint64_t*>(mask);
+    uint64_t* to = static_cast<uint64_t*>(toff);
+    VXG_TRY(launch_filter_count(m, n, to, s_));
+    uint64_t k = 0;
+    VXG_TRY(hip_check(hipMemcpyAsync(&k, to + tiles, 8, hipMemcpyDeviceToHost, s_), "filter count readback"));
+    VXG_TRY(hip_check(hipStreamSynchronize(s_), "filter count sync"));
+
+    // canonical source in temporaries
+    vxg_canonical src{};
+    const vxg_array* vnode;
+    int vkind;
+    VXG_TRY(validity_source(a, &vnode, &vkind));
+    if (vkind != 0) VXG_TRY(temp(((n + 31) / 32) * 4, &src.validity));
+    std::vector<vxg_data_buffer> bufs;
+    if (is_str) {
+        uint64_t extent;
+        VXG_TRY(string_layout(a, bufs, extent));
+        VXG_TRY(temp(16 * n, &src.views));
+        VXG_TRY(temp(extent + 16, &src.data));
+        src.data_bytes = extent;
+        src.data_buffers = bufs.data();
+        src.n_data_buffers = src.data_buffers_cap = uint32_t(bufs.size());
+    } else if (a.dtype == VXG_DTYPE_BOOL) {
+        VXG_TRY(temp(((n + 31) / 32) * 4, &src.values));
+    } else {
+        VXG_TRY(temp(n * width(a), &src.values));
+    }
+    VXG_TRY(canonical(a, src));
+
+    out.kind = src.kind;
+    out.len = k;
+    out.dtype = a.dtype;
+    out.ptype = a.ptype;
+    const uint64_t vbits = ((k + 31) / 32) * 4;
+    if (src.validity) {  // validity.filter(predicate)
+        if (!out.validity) VXG_TRY(hip_check(hipMalloc(&out.validity, vbits ? vbits : 4), "filter validity alloc"));
+        VXG_TRY(launch_copy_bytes(out.validity, nullptr, vbits ? vbits : 4, s_));
+        VXG_TRY(launch_filter_bits(m, n, to, static_cast<const uint8_t*>(src.validity), out.validity, s_));
+    } else {
+        out.validity = nullptr;
+    }
+    if (a.dtype == VXG_DTYPE_PRIMITIVE) {
+        out.values_bytes = k * width(a);
+        if (!out.values)
+            VXG_TRY(hip_check(hipMalloc(&out.values, out.values_bytes ? out.values_bytes : 16), "filter values alloc"));
+        return launch_filter_values(m, n, to, src.values, width(a), out.values, s_);
+    }
+    if (a.dtype == VXG_DTYPE_BOOL) {
+        out.values_bytes = vbits;
+        if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, vbits ? vbits : 4), "filter bool alloc"));
+        VXG_TRY(launch_copy_bytes(out.values, nullptr, vbits ? vbits : 4, s_));
+        return launch_filter_bits(m, n, to, static_cast<const uint8_t*>(src.values), out.values, s_);
+    }
+    // strings: compact the views, then rebuild one heap of the selected rows
+    if (!out.views) VXG_TRY(hip_check(hipMalloc(&out.views, k ? 16 * k : 16), "filter views alloc"));
+    VXG_TRY(launch_filter_values(m, n, to, src.views, 16, out.views, s_));
+    const uint64_t ktiles = filter_tiles(k);
+    void* hoff;
+    VXG_TRY(temp((ktiles + 1) * 8, &hoff));
+    uint8_t* views = static_cast<uint8_t*>(out.views);
+    const uint8_t* valid = static_cast<const uint8_t*>(out.validity);
+    VXG_TRY(launch_view_heap_sizes(views, k, valid, static_cast<uint64_t*>(hoff), s_));
+    uint64_t heap = 0;
+    VXG_TRY(hip_check(hipMemcpyAsync(&heap, static_cast<uint64_t*>(hoff) + ktiles, 8, hipMemcpyDeviceToHost, s_),
+                      "filter heap readback"));
+    VXG_TRY(hip_check(hipStreamSynchronize(s_), "filter heap sync"));
+    if (heap > 0xFFFFFFFFull) return set_error(VXG_ERR_INVALID_ARGUMENT, "filtered string heap exceeds u32 view offsets");
+    if (out.data && out.data_bytes < heap)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "caller-provided data holds " + std::to_string(out.data_bytes) +
+                                                       " bytes, the filtered heap needs " + std::to_string(heap));
+    if (!out.data) VXG_TRY(hip_check(hipMalloc(&out.data, heap + 16), "filter heap alloc"));
+    out.data_bytes = heap;
+    out.n_data_buffers = 1;
+    if (out.data_buffers && out.data_buffers_cap >= 1) out.data_buffers[0] = vxg_data_buffer{0, heap};
+    std::vector<const uint8_t*> bases(bufs.size());
+    for (size_t i = 0; i < bufs.size(); ++i) bases[i] = static_cast<const uint8_t*>(src.data) + bufs[i].offset;
+    void* dbases;
+    VXG_TRY(temp(bases.size() * sizeof(void*) + 8, &dbases));
+    if (!bases.empty())
+        VXG_TRY(hip_check(hipMemcpyAsync(dbases, bases.data(), bases.size() * sizeof(void*), hipMemcpyHostToDevice, s_),
+                          "filter buffer table upload"));
+    VXG_TRY(launch_view_heap_build(views, k, valid, static_cast<uint64_t*>(hoff),
+                                   static_cast<const uint8_t* const*>(dbases), uint32_t(bases.size()),
+                                   static_cast<uint8_t*>(out.data), ctx_->c.err_word, s_));
+    return hip_check(hipStreamSynchronize(s_), "filter sync");  // `bases` is read by the upload
+}
+
+}  // namespace vxg

@@ -4,13 +4,13 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/vortex_gpu.h"
+#include "env.hpp"
 
 namespace vxg {
 
@@ -135,7 +135,7 @@ inline Options cur_options() { return g_cur_ctx ? g_cur_ctx->opt : default_optio
 inline int k1_wave_mode() {
     const int64_t o = cur_options().k1_wave;
     if (o >= 0) return int(o > 2 ? 2 : o);
-    const char* e = std::getenv("VXG_K1_WAVE");
+    const char* e = env_str("VXG_K1_WAVE");
     if (!e) return 1;
     return e[0] == '0' ? 0 : (e[0] == 'f' ? 2 : 1);
 }
@@ -219,13 +219,9 @@ __device__ __forceinline__ uint32_t ext_chunk_index_gpe(const E* __restrict__ ex
     return ext_chunk_index(ext, n, g, key);
 }
 // Host side: the common workgroup count of a table's entries (all but the last equal, the last
-// not larger), else 0.  VXG_EXT_GPE=0 (read once) disables the direct lookup (A/B).
+// not larger), else 0.
 inline uint64_t common_groups(const uint64_t* counts, size_t n) {
-    static const bool on = [] {
-        const char* e = std::getenv("VXG_EXT_GPE");
-        return !(e && e[0] == '0');
-    }();
-    if (!on || n == 0 || counts[0] == 0) return 0;
+    if (n == 0 || counts[0] == 0) return 0;
     for (size_t i = 1; i + 1 < n; i++)
         if (counts[i] != counts[0]) return 0;
     return counts[n - 1] <= counts[0] ? counts[0] : 0;
@@ -319,10 +315,7 @@ extern thread_local bool g_k1w_wrote_patches;
 // (round 5: the C3 8-GPU shard's 32-chunk kernel-argument launch is exactly 512 workgroups of 32
 // blocks, one per two CUs' worth of waves); VXG_SPLIT_BELOW overrides (read once).
 inline uint64_t split_below_groups() {
-    static const uint64_t v = [] {
-        const char* e = std::getenv("VXG_SPLIT_BELOW");
-        return e ? uint64_t(std::strtoull(e, nullptr, 10)) : uint64_t(1024);
-    }();
+    static const uint64_t v = env_u64("VXG_SPLIT_BELOW", 1024);
     return v;
 }
 // Whether launch_fl_unpack takes K1w for a kernel-argument table of `groups32` 32-block workgroups.
@@ -366,14 +359,14 @@ vxg_status fl_plain_16(int W, Epi epi, const ChunkTable& t, uint64_t g, hipStrea
 vxg_status fl_plain_32(int W, Epi epi, const ChunkTable& t, uint64_t g, hipStream_t s);
 vxg_status fl_plain_64(int W, Epi epi, const ChunkTable& t, uint64_t g, hipStream_t s);
 vxg_status fl_alp(int T, int W, Epi epi, const ChunkTable& t, uint64_t g, hipStream_t s);
-// K14: Dict(codes=BitPacked) with 8/16-byte values, thread per output (dict_rows.hip)
-vxg_status launch_dict_rows(int T, int W, int vw, const ChunkTable& tab, hipStream_t s);
+// K14: Dict(codes=BitPacked) with 16-byte values (the views of a string dictionary), thread per
+// output (dict_rows.hip)
+vxg_status launch_dict_rows(int T, int W, const ChunkTable& tab, hipStream_t s);
 #define VXG_DECL_DICT(VW) vxg_status fl_dict_##VW(int T, int W, const ChunkTable& t, uint64_t g, hipStream_t s);
 VXG_DECL_DICT(1)
 VXG_DECL_DICT(2)
 VXG_DECL_DICT(4)
 VXG_DECL_DICT(8)
-VXG_DECL_DICT(16)
 #undef VXG_DECL_DICT
 constexpr int kDictFusedMaxW = 16;
 vxg_status launch_delta(int width, const void* bases, const void* deltas, uint64_t n_deltas,
