@@ -469,6 +469,28 @@ def test_k1w_fused_patches_unsorted_cluster_never_writes_out_of_range(k1w, mode)
     ctx.sync()  # the error word was cleared by the failing sync
 
 
+# Whether ALP's outer patches ride the K1 launch is decided before the launch by the rule that
+# picks the launch's kernel (k1_choose, vxg_internal.hpp): K1w writes them, every other kernel
+# leaves them to the scatter.  The same arrays under every K1_WAVE mode; mode 0 never takes K1w.
+@pytest.mark.parametrize("wave", [0, 1, 2])
+@pytest.mark.parametrize("n", [1025, 70_000])
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+def test_fused_patch_decision_every_wave_mode(ctx, f32, n, wave):
+    rng = np.random.default_rng(1000 * n + 10 * wave + f32)
+    arr, expect = _alp_patched(rng, n, np.unique([0, 1023, 1024, n - 1]), f32=f32)
+    ctx.set_option("k1_wave", wave)
+    ctx.launch_stats(reset=True)
+    try:
+        assert_primitive_parity(arr, ctx, expect)
+        st = ctx.launch_stats(reset=True)
+    finally:
+        ctx.set_option("k1_wave", -1)
+    if wave == 2:
+        assert st["k1w_launches"] >= 1
+    if wave == 0:
+        assert st["k1w_launches"] == 0
+
+
 def test_plan_measure_flag_and_info(ctx):
     """vxg_plan_create executes nothing and records one candidate; VXG_PLAN_MEASURE records both,
     times them and reports a device error found by its runs from create itself."""
@@ -1694,6 +1716,79 @@ def test_plan_nested_chunked_not_deferred(ctx):
         assert res[-1].numpy()[0].tobytes() == rviews.tobytes()
         assert [b.tobytes() for b in res[-1].buffers()] == [b.tobytes() for b in rbufs]
     plan.close()
+
+
+def _alp_inner_outer(vals, outer, outer_vals):
+    """ALP(FoR(BitPacked with inner patches)) whose outer patches sit at `outer` (ascending):
+    the BitPacked width holds the small encoded values only, so every large one is an inner patch."""
+    e, f, enc, idx, _ = E.alp_encode(vals)
+    u, ref, sh = E.for_compress(enc)
+    bp = E.encode_bitpacked(u, bit_width=int(np.median(u)).bit_length() + 1)
+    assert bp.meta["has_patches"]
+    pos = np.union1d(outer, idx).astype(np.int64)  # the encoder's own exceptions are patches too
+    pv = vals[pos].copy()
+    pv[np.isin(pos, outer)] = outer_vals
+    ind = pos.astype(np.uint64)
+    ia = E.encode_bitpacked(ind, bit_width=max(1, int(ind.max()).bit_length()), allow_patches=False)
+    patches = A.sparse(ia, A.primitive(pv, validity="ALL_VALID"), vals.size)
+    return A.alp(A.frame_of_reference(bp, ref, sh, "i64"), e, f, patches)
+
+
+def test_patch_order_inner_then_outer_single_chunked_plan(ctx):
+    """A position with an inner (BitPacked) and an outer (ALP) patch ends with the outer value:
+    as one array (launched at once), as chunks (K1 decodes and both scatters queued by the chunk
+    loop, in that order) and through a plan in either batch mode."""
+    import torch
+    rng = np.random.default_rng(515)
+    n, cuts = 3000, [0, 1000, 2100, 3000]
+    vals = np.round(rng.uniform(1, 1000, n) * 100) / 100
+    inner = np.sort(rng.choice(n, 60, replace=False))
+    inner[:6] = [3, 999, 1000, 1500, 2100, 2999]
+    inner = np.unique(inner)
+    vals[inner] = np.round(rng.uniform(1e7, 1e8, inner.size) * 100) / 100
+    # two positions per chunk that carry an inner patch too, and some that do not
+    outer = np.unique(np.concatenate([[3, 999, 1000, 1500, 2100, 2999, 0, 1023, 1024, 2098], rng.choice(n, 20)]))
+    assert np.isin(outer, inner).sum() >= 6
+    outer_vals = rng.standard_normal(outer.size) * 1e9 + 0.123456789
+    expect = vals.copy()
+    expect[outer] = outer_vals
+
+    single = _alp_inner_outer(vals, outer, outer_vals)
+    chunks = []
+    for a, b in zip(cuts, cuts[1:]):
+        m = (outer >= a) & (outer < b)
+        chunks.append(_alp_inner_outer(vals[a:b], outer[m] - a, outer_vals[m]))
+    chunked = A.chunked(chunks)
+    assert_primitive_parity(single, ctx, expect)
+    assert_primitive_parity(chunked, ctx, expect)
+    for mode in ("0", "1"):
+        with plan_mode(mode):
+            plan = V.Plan([chunked.to(torch.device("cuda", 0))], ctx)
+        assert_primitive_parity(chunked, ctx, expect, res=plan.launch(sync=True)[0])
+        plan.close()
+
+
+def test_chunked_fsst_sink_stops_at_nested_strings(ctx):
+    """FSST chunks of a chunked string array decode together after the chunk loop; the FSST
+    VALUES of a Dict chunk between them do not join that list: they decode at once, before the
+    take that reads their views.  One-shot and through a plan in either batch mode."""
+    import torch
+    rng = np.random.default_rng(616)
+    parts = [_comment_strings(rng, 2000 + 100 * c, vocab=30 + c) for c in range(3)]
+    uniq = sorted(set(parts[1]))
+    pos = {s: i for i, s in enumerate(uniq)}
+    codes = np.array([pos[s] for s in parts[1]], dtype=np.uint32)
+    arr = A.chunked([E.encode_fsst(parts[0]),
+                     A.dict_array(E.encode_fsst(uniq), E.encode_bitpacked(codes, allow_patches=False)),
+                     E.encode_fsst(parts[2])])
+    assert [c.encoding for c in arr.children[1:]] == [A.ENC["FSST"], A.ENC["DICT"], A.ENC["FSST"]]
+    strings = parts[0] + parts[1] + parts[2]
+    assert_string_parity(arr, ctx, strings)
+    for mode in ("0", "1"):
+        with plan_mode(mode):
+            plan = V.Plan([arr.to(torch.device("cuda", 0))], ctx)
+        assert_string_parity(arr, ctx, strings, res=plan.launch(sync=True)[0])
+        plan.close()
 
 
 def test_varbin_bad_offsets_is_an_error(ctx):

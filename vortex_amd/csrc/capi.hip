@@ -85,7 +85,7 @@ static vxg_status bitunpack_common(vxg_ctx* ctx, int T, unsigned W, unsigned off
                                    UnpackArgs a, void* out, void* stream) {
     std::vector<K1Job> jobs(1);
     VXG_TRY(make_k1_job(T, W, offset, len, packed, packed_bytes, epi, vw, a, out, jobs[0]));
-    return launch_k1_jobs(jobs, ctx->c.err_word, S(stream));
+    return launch_k1_jobs(jobs, ctx->c.err_word, S(stream), nullptr, nullptr);
 }
 
 extern "C" {
@@ -337,7 +337,7 @@ vxg_status vxg_bitunpack_dict_chunks(vxg_ctx* ctx, int codes_ptype, unsigned bit
         VXG_TRY(make_k1_job(unsigned_T(codes_ptype), bit_width, 0, c.len, c.packed, c.n_blocks * 128ull * bit_width,
                             Epi::Dict, int(value_width), a, c.out, jobs[i]));
     }
-    return launch_k1_jobs(jobs, ctx->c.err_word, S(stream));
+    return launch_k1_jobs(jobs, ctx->c.err_word, S(stream), nullptr, nullptr);
 }
 
 vxg_status vxg_patch(vxg_ctx* ctx, int ptype, void* out, uint64_t out_len, int indices_ptype, const void* indices,

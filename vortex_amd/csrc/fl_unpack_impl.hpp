@@ -793,9 +793,6 @@ vxg_status launch_w(ChunkTable tab, hipStream_t s) {
                             : size_t(W > 0 ? BPW * 128 * W : 0) + 128;
     hipLaunchKernelGGL((fl_unpack_w_kernel<T, W, EPI, VW, LDSD, EXT>), dim3(unsigned(groups)), dim3(256), shm, s, tab);
     note_k1w_launch(uint32_t(BPW), uint32_t(BPW_MAX), groups);
-    if constexpr (!EXT) {
-        if (tab.patch.n) g_k1w_wrote_patches = true;  // only this kernel reads tab.patch
-    }
     return hip_check(hipGetLastError(), "fl_unpack_w_kernel launch");
 }
 
@@ -819,54 +816,50 @@ vxg_status launch_s(ChunkTable tab, hipStream_t s) {
     return hip_check(hipGetLastError(), "fl_unpack_kernel launch");
 }
 
-// `groups32` = the table's workgroups at 32 blocks per workgroup (decides the row split).
+// `groups32` = the table's workgroups at 32 blocks per workgroup.  k1_choose (vxg_internal.hpp)
+// decides the kernel; this function only instantiates and launches what it chose.
 template <int T, int W, Epi EPI, int VW>
 vxg_status launch_one(const ChunkTable& tab, uint64_t groups32, hipStream_t s) {
-    if (groups32 == 0) return VXG_OK;
     constexpr bool kSplit = (T == 32 || T == 64) && W > 0;
-    const bool split = kSplit && groups32 < split_below_groups();
-    bool lds = false;
+    bool lds_ok = false;
     if constexpr (EPI == Epi::Dict) {
         const ChunkDev* cs = tab.ext ? tab.host : tab.c;
-        lds = true;
+        lds_ok = true;
         for (uint32_t k = 0; k < tab.n; k++)
-            lds = lds && cs[k].dict_len * VW <= uint64_t(kDictLdsBytes) &&
-                  (reinterpret_cast<uintptr_t>(cs[k].dict) & 15) == 0;
+            lds_ok = lds_ok && cs[k].dict_len * VW <= uint64_t(kDictLdsBytes) &&
+                     (reinterpret_cast<uintptr_t>(cs[k].dict) & 15) == 0;
     }
-    // Dict gathers keep the register-resident K1 by default: C3 (u64 codes W=10, 8-byte values,
-    // dictionary in LDS) measured 0.65 of 8 TB/s with K1w against 0.70 with the row split
-    // Device-table launches (a plan's chunked columns) take K1w from kExtWaveGroups workgroups of
-    // 32 blocks: C5's 48 MB numeric columns (183) measured C5 0.52 -> 0.556 of 8 TB/s with K1w
-    // instead of the row split (sessions r04kw, r04c), but the 2-GPU shard's halves (92) 0.506 ->
-    // 0.429 (too few K1w workgroups for 256 CUs)
-    constexpr uint64_t kExtWaveGroups = 128;
-    const int mode = k1_wave_mode();
-    const bool big = !split || (tab.ext && groups32 >= kExtWaveGroups);
-    const bool wave = mode == 2 || (mode == 1 && big && EPI != Epi::Dict);  // large launches: K1w
+    const K1Choice c = k1_choose(T, W, EPI, tab.ext != nullptr, groups32, lds_ok, k1_wave_mode(), split_below_groups());
+    const bool wave = c.kind == K1Kind::Wave;
+    // only the kernel-argument K1w writes tab.patch: no other choice may drop the patches silently
+    if (tab.patch.n && (!wave || tab.ext))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "internal: patches handed to a K1 launch that does not write them");
+    if (c.kind == K1Kind::None) return VXG_OK;
     if (tab.ext) {  // device table (plans): K1w, or the register-resident K1 for Dict gathers
         if (wave) {
             if constexpr (EPI == Epi::Dict) {
-                if (lds) return launch_w<T, W, EPI, VW, true, true>(tab, s);
+                if (c.lds) return launch_w<T, W, EPI, VW, true, true>(tab, s);
             }
             return launch_w<T, W, EPI, VW, false, true>(tab, s);
         }
         constexpr int SX = kSplit ? 4 : 1;
         if constexpr (EPI == Epi::Dict) {
-            if (lds) return launch_s<T, W, EPI, VW, true, SX, true>(tab, s);
+            if (c.lds) return launch_s<T, W, EPI, VW, true, SX, true>(tab, s);
         }
         return launch_s<T, W, EPI, VW, false, SX, true>(tab, s);
     }
     if constexpr (kSplit) {
-        if (split && !wave) return lds ? launch_s<T, W, EPI, VW, true, 4>(tab, s) : launch_s<T, W, EPI, VW, false, 4>(tab, s);
+        if (c.kind == K1Kind::RegSplit)
+            return c.lds ? launch_s<T, W, EPI, VW, true, 4>(tab, s) : launch_s<T, W, EPI, VW, false, 4>(tab, s);
     }
     if (wave) {
         if constexpr (EPI == Epi::Dict) {
-            if (lds) return launch_w<T, W, EPI, VW, true, false>(tab, s);
+            if (c.lds) return launch_w<T, W, EPI, VW, true, false>(tab, s);
         }
         return launch_w<T, W, EPI, VW, false, false>(tab, s);
     }
     if constexpr (EPI == Epi::Dict) {
-        if (lds) return launch_s<T, W, EPI, VW, true, 1>(tab, s);
+        if (c.lds) return launch_s<T, W, EPI, VW, true, 1>(tab, s);
     }
     return launch_s<T, W, EPI, VW, false, 1>(tab, s);
 }

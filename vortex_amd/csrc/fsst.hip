@@ -1112,7 +1112,7 @@ uint64_t fsst_scratch_bytes(uint64_t n) {
     return (2 * n_tiles + (n_tiles + kScanTiles - 1) / kScanTiles + 2) * sizeof(int64_t);
 }
 
-uint64_t fsst_batch_scratch_bytes(const FsstChunk* chunks, size_t n_chunks) {
+uint64_t fsst_chunks_scratch_bytes(const FsstChunk* chunks, size_t n_chunks) {
     uint64_t b = 16;
     for (size_t i = 0; i < n_chunks; i++) b += fsst_scratch_bytes(chunks[i].n);
     return b;

@@ -103,9 +103,15 @@ uint32_t gen_runs_lds_bytes(int value_width) {
     }
 }
 
-vxg_status launch_k1_generic(const GenChunk* ext, uint32_t n, uint64_t groups, bool dict_lds, uint32_t packed_bytes,
-                             uint32_t dict_bytes, uint32_t runs_bytes, uint32_t* err, hipStream_t s,
-                             uint64_t gpe, const FsstFused* fuse) {
+// One launch over a device table of n jobs (first_group filled in).  `dict_lds` = every Dict
+// job's dictionary fits the LDS stage (16 KiB, 16-byte aligned); packed_bytes / dict_bytes /
+// runs_bytes = the largest packed stage (bpw * 128 * W), dictionary stage (staged dictionaries,
+// VarBin views) and RunEnd expansion LDS of the launch's jobs.
+// With `fuse` valid, the launch also decodes that FSST group's tiles (fsst.hip fsst_k1g_kernel;
+// n = 0 is allowed then).
+static vxg_status launch_k1_generic(const GenChunk* ext, uint32_t n, uint64_t groups, bool dict_lds,
+                                    uint32_t packed_bytes, uint32_t dict_bytes, uint32_t runs_bytes, uint32_t* err,
+                                    hipStream_t s, uint64_t gpe, const FsstFused* fuse) {
     static_assert(kGenVarBinDictMax * 16 <= uint64_t(kDictLdsBytes), "VarBin views must fit the dictionary stage");
     if (n == 0) groups = 0;
     if (groups == 0 && !(fuse && fuse->valid)) return VXG_OK;
@@ -122,6 +128,84 @@ vxg_status launch_k1_generic(const GenChunk* ext, uint32_t n, uint64_t groups, b
     hipLaunchKernelGGL(k1_generic_kernel, dim3(unsigned(groups)), dim3(kGenThreads), shm, s, ext, n, dict_off, dict_lds,
                        err, gpe);
     return hip_check(hipGetLastError(), "k1_generic_kernel launch");
+}
+
+// The table of one K1g launch and the launch itself: a GenChunk per job of `gen` (none empty) and
+// per expansion of `gen_runs` (value width, chunk), beside `fuse`'s FSST tiles when it is valid.
+vxg_status launch_k1g_jobs(const std::vector<const K1Job*>& gen, const std::vector<std::pair<int, RunEndChunk>>& gen_runs,
+                           const FsstFused& fuse, uint32_t* err, hipStream_t s, DevTables& dt) {
+    const size_t n_runs = gen_runs.size();
+    if (gen.empty() && !n_runs && !fuse.valid) return VXG_OK;
+    if (gen.size() + n_runs > 0xFFFFFFFFull) return set_error(VXG_ERR_INVALID_ARGUMENT, "too many chunks");
+    GenChunk* host;
+    const GenChunk* ext;
+    if (const vxg_status st = dt.table(gen.size() + n_runs, &host, &ext); st != VXG_OK) return st;
+    uint64_t groups = 0;
+    bool dict_lds = true;
+    uint32_t packed_bytes = 0, dict_bytes = 0, runs_bytes = 0;
+    // a launch of string-dictionary jobs alone (an unbatched plan's chunked Dict(VarBin)
+    // column): one FastLanes block of codes per workgroup (gen_vb_bpw)
+    const bool vb_alone = n_runs == 0 && !fuse.valid &&
+                          std::all_of(gen.begin(), gen.end(), [](const K1Job* jp) { return jp->vb; });
+    uint64_t gen_blocks = 0;
+    for (const K1Job* jp : gen) gen_blocks += jp->d.n_blocks;
+    const uint32_t bpw_cap = gen_bpw_cap(gen_blocks);
+    for (size_t k = 0; k < gen.size(); k++) {
+        const K1Job& jb = *gen[k];
+        GenChunk& g = host[k];
+        g.d = jb.d;
+        g.kind = uint32_t(gen_kind(jb.T, int(jb.epi), jb.vw, jb.vb));
+        g.W = uint32_t(jb.W);
+        g.bpw = jb.vb ? gen_vb_bpw(jb.T, jb.W, vb_alone, bpw_cap) : gen_bpw(jb.T, jb.W, bpw_cap);
+        g.d.first_group = groups;
+        groups += (jb.d.n_blocks + g.bpw - 1) / g.bpw;
+        packed_bytes = std::max(packed_bytes, g.bpw * 128u * uint32_t(jb.W));
+        if (jb.vb) {
+            dict_bytes = std::max(dict_bytes, gen_vb_stage_bytes(jb.d.dict_len, jb.vbc.bytes));
+            g.vb_src = jb.vbc.src;
+            g.vb_offs = jb.vbc.offsets;
+            g.vb_offs_width = jb.vbc.offs_width;
+            g.vb_dst = jb.vbc.dst;
+            g.vb_bytes = jb.vbc.bytes;
+            g.vb_bidx = jb.vbc.bidx;
+        } else if (jb.epi == Epi::Dict) {
+            dict_lds = dict_lds && jb.d.dict_len * uint64_t(jb.vw) <= uint64_t(kDictLdsBytes) &&
+                       (reinterpret_cast<uintptr_t>(jb.d.dict) & 15) == 0;
+        }
+    }
+    if (dict_lds)  // every plain Dict job stages its dictionary
+        for (const K1Job* jp : gen)
+            if (jp->epi == Epi::Dict && !jp->vb)
+                dict_bytes = std::max(dict_bytes, uint32_t((jp->d.dict_len * uint64_t(jp->vw) + 15) & ~15ull));
+    for (size_t k = 0; k < n_runs; k++) {  // short-run RunEnd expansions (runend_runs.hpp)
+        const auto& [w, r] = gen_runs[k];
+        GenChunk& g = host[gen.size() + k];
+        g.kind = uint32_t(gen_runs_kind(w));
+        g.re = r;
+        g.d.first_group = groups;
+        g.d.n_blocks = r.n_runs;  // (unused by the body; keeps the entry self-describing)
+        groups += (r.n_runs + kRunEndRunsPerGroup - 1) / kRunEndRunsPerGroup;
+        runs_bytes = std::max(runs_bytes, gen_runs_lds_bytes(w));
+    }
+    std::vector<uint64_t> cnt(gen.size() + n_runs);  // workgroups per job (direct job lookup when equal)
+    for (size_t k = 0; k < cnt.size(); k++)
+        cnt[k] = (k + 1 < cnt.size() ? host[k + 1].d.first_group : groups) - host[k].d.first_group;
+    uint64_t gpe = common_groups(cnt.data(), cnt.size());
+    // Nearly equal counts (C5's RunEnd chunks: 16 or 17 workgroups; every column's last chunk
+    // smaller): every job padded to the largest count when that adds <= 1/10 idle workgroups,
+    // so a workgroup finds its job by one division instead of a wave-wide search over the
+    // table (one or more dependent round trips before its loads; gen_dispatch returns at once
+    // on a padding workgroup).
+    if (!gpe && cnt.size() > 1) {
+        const uint64_t m = *std::max_element(cnt.begin(), cnt.end());
+        if (m * cnt.size() - groups <= groups / 10) {
+            for (size_t k = 0; k < cnt.size(); k++) host[k].d.first_group = k * m;
+            groups = m * cnt.size();
+            gpe = m;
+        }
+    }
+    return launch_k1_generic(ext, uint32_t(gen.size() + n_runs), groups, dict_lds, packed_bytes, dict_bytes, runs_bytes,
+                             err, s, gpe, &fuse);
 }
 
 }  // namespace vxg

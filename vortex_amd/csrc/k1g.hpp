@@ -13,6 +13,19 @@
 
 namespace vxg {
 
+// One K1 decode (a whole BitPacked-rooted cascade of one array or one chunk) and the kernel
+// it needs.  Jobs with the same kernel share launches.
+struct K1Job {
+    int T, W;
+    Epi epi;
+    int vw;
+    ChunkDev d;
+    // a plan batch's Dict over a small VarBin dictionary: K1g builds the dictionary's views
+    // (d.dict unused) and copies its bytes (vb.src -> vb.dst); only K1g runs such a job
+    bool vb = false;
+    VarBinChunk vbc{};
+};
+
 struct GenChunk {
     ChunkDev d;        // first_group = first workgroup of this job in the launch
     uint32_t kind;     // body index (gen_kind)
@@ -61,15 +74,9 @@ uint32_t gen_bpw_cap(uint64_t blocks);
 uint32_t gen_vb_bpw(int T, int W, bool alone, uint32_t cap = 0);
 // LDS a short-run RunEnd expansion of `value_width`-byte values needs.
 uint32_t gen_runs_lds_bytes(int value_width);
-// One launch over a device table of n jobs (first_group filled in).  `dict_lds` = every Dict
-// job's dictionary fits the LDS stage (16 KiB, 16-byte aligned); packed_bytes / dict_bytes /
-// runs_bytes = the largest packed stage (bpw * 128 * W), dictionary stage (staged dictionaries,
-// VarBin views) and RunEnd expansion LDS of the launch's jobs.
-// With `fuse` valid, the launch also decodes that FSST group's tiles (fsst.hip fsst_k1g_kernel;
-// n = 0 is allowed then).
-vxg_status launch_k1_generic(const GenChunk* ext, uint32_t n, uint64_t groups, bool dict_lds, uint32_t packed_bytes,
-                             uint32_t dict_bytes, uint32_t runs_bytes, uint32_t* err, hipStream_t s,
-                             uint64_t gpe = 0, const FsstFused* fuse = nullptr);
+// One K1g launch over a new device table of `dt` (k1g.hip); nothing to decode: no launch.
+vxg_status launch_k1g_jobs(const std::vector<const K1Job*>& gen, const std::vector<std::pair<int, RunEndChunk>>& gen_runs,
+                           const FsstFused& fuse, uint32_t* err, hipStream_t s, DevTables& dt);
 // The fused launch (fsst.hip): K1g jobs `ext` (n entries, `groups` workgroups, LDS `shm` with the
 // dictionary stage at dict_off) beside `fuse`'s decode tiles.
 vxg_status launch_fsst_k1g(const FsstFused& fuse, const GenChunk* ext, uint32_t n, uint64_t groups, uint32_t dict_off,

@@ -8,6 +8,12 @@
 // recognises the cascade and issues ONE fused K1 launch (+ tiny patch scatters); anything it
 // does not recognise is decoded child-first into temporaries exactly like the reference.
 //
+// No decode decision travels in Planner state.  A decode function launches at once unless its
+// caller hands it a sink (K1Sink below; strings_into's FSST chunk list): only the chunk loop of a
+// ChunkedArray makes one, and it reaches only the BitPacked leaf of a chunk that is one K1 decode.
+// Which K1 kernel a launch takes is one rule, k1_choose (vxg_internal.hpp): launch_one switches on
+// it and decode_alp asks it beforehand whether the launch will write its outer patches.
+//
 // Units: planner_launch.hip (launch grouping, K1 dispatch), planner_decode.hip (primitives,
 // validity, bools, canonical()), planner_strings.hip, planner_compute.hip (take, filter, compare),
 // plan.hip (the plan recorder), capi.hip (the context and the C entry points).
@@ -23,6 +29,7 @@
 #include "compare.hpp"
 #include "compare_str.hpp"
 #include "env.hpp"
+#include "k1g.hpp"
 #include "take.hpp"
 #include "vxg_internal.hpp"
 
@@ -49,19 +56,6 @@ vxg_status status_of_err_word(uint32_t err);
 
 inline bool is_string(const vxg_array& a) { return a.dtype == VXG_DTYPE_UTF8 || a.dtype == VXG_DTYPE_BINARY; }
 
-// One K1 decode (a whole BitPacked-rooted cascade of one array or one chunk) and the kernel
-// it needs.  Jobs with the same kernel share launches.
-struct K1Job {
-    int T, W;
-    Epi epi;
-    int vw;
-    ChunkDev d;
-    // a plan batch's Dict over a small VarBin dictionary: K1g builds the dictionary's views
-    // (d.dict unused) and copies its bytes (vb.src -> vb.dst); only K1g runs such a job
-    bool vb = false;
-    VarBinChunk vbc{};
-};
-
 // A recorded plan's deferred launches, shared by the planners of all its arrays: the K1 decodes,
 // RunEnd expansions and string-dictionary views of every chunked column, launched together at
 // the end of recording on one graph branch (dictionary views, then one launch per large K1 kernel
@@ -83,15 +77,31 @@ struct PlanBatch {
 // Validate one BitPacked buffer (bitpacking/mod.rs:54-130) and describe its K1 decode.
 vxg_status make_k1_job(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
                        Epi epi, int vw, const UnpackArgs& a, void* out, K1Job& j);
-// K1 jobs grouped by kernel; dt: the plan being recorded; generic_small: a plan's batch, whose
-// small groups share one K1g launch with gen_runs and the fused FSST group.
-vxg_status launch_k1_jobs(std::vector<K1Job>& jobs, uint32_t* err, hipStream_t s, DevTables* dt = nullptr,
-                          bool generic_small = false,
-                          const std::vector<std::pair<int, RunEndChunk>>* gen_runs = nullptr,
-                          const PatchCol* patch = nullptr, const FsstFused* fuse = nullptr);
+// K1 jobs launched now, grouped by kernel; dt: the plan being recorded, or null; patch: the outer
+// patches of the single array that `jobs` decodes, written by its K1w launch (k1_choose), or null.
+vxg_status launch_k1_jobs(std::vector<K1Job>& jobs, uint32_t* err, hipStream_t s, DevTables* dt, const PatchCol* patch);
 vxg_status launch_runs(std::vector<RunEndChunk> runs, int w, uint32_t* err, hipStream_t s, DevTables* dt);
 vxg_status launch_varbin_dicts(const std::vector<VarBinChunk>& dicts, uint32_t* err, hipStream_t s, DevTables* dt);
 vxg_status flush_plan_batch(PlanBatch& b, uint32_t* err, hipStream_t s, DevTables* dt);
+
+// ---- decode sinks ----------------------------------------------------------------------------
+// A patch scatter that must follow a queued K1 decode.
+struct PatchJob {
+    const vxg_array* sp;
+    int T;
+    Epi epi;
+    int vw;
+    UnpackArgs a;
+    void* dst;
+    uint64_t out_len;
+};
+// Where the K1 decode of a single-K1 cascade (Planner::k1_fusable) goes instead of its own launch:
+// into the chunk loop's shared launches, its patch scatters after them in queue order.  A decode
+// function launches at once unless it is handed a sink, and hands it on only to the BitPacked
+// leaf of that cascade -- never to a child it decodes into a temporary -- so no nested array can
+// queue into a loop that does not know of it.  The FSST chunks of a chunked string array travel
+// the same way (strings_into's std::vector<FsstChunk>*).
+struct K1Sink { std::vector<K1Job>& jobs; std::vector<PatchJob>& patches; };
 
 // ===================================================================================
 // Planner
@@ -136,21 +146,7 @@ class Planner {
     // after it, so it launches immediately.
     const vxg_array* root_ = nullptr;
     bool defer(const vxg_array& a) const { return batch_ && &a == root_; }
-    // Deferred K1 decodes of the chunks of a ChunkedArray (grouped into shared launches) and
-    // the patch scatters that must follow them; null = launch immediately.
-    struct PatchJob {
-        const vxg_array* sp;
-        int T;
-        Epi epi;
-        int vw;
-        UnpackArgs a;
-        void* dst;
-        uint64_t out_len;
-    };
-    std::vector<K1Job>* k1_batch_ = nullptr;
-    std::vector<PatchJob>* patch_batch_ = nullptr;
-    const PatchCol* fused_patch_ = nullptr;  // decode_alp -> decode_bitpacked: patches K1w writes
-    std::vector<FsstChunk>* fsst_batch_ = nullptr;  // FSST chunks of a chunked string array
+    // `c` decodes as one K1 launch (+ patch scatters): what a K1Sink may be handed to.
     bool k1_fusable(const vxg_array& c) const;
 
     vxg_status temp(uint64_t bytes, void** p) {
@@ -175,8 +171,9 @@ class Planner {
         return i < a.n_children ? &a.children[i] : nullptr;
     }
 
-    // Decode a primitive-typed array into dst (len * width bytes, 16-B aligned).
-    vxg_status decode_into(const vxg_array& a, void* dst);
+    // Decode a primitive-typed array into dst (len * width bytes, 16-B aligned).  With a sink, `a`
+    // is k1_fusable and its one K1 decode is queued (K1Sink).
+    vxg_status decode_into(const vxg_array& a, void* dst, K1Sink* sink = nullptr);
     // Canonical primitive values of `a` as a device pointer (aliases PRIMITIVE buffers).
     vxg_status view_primitive(const vxg_array& a, const void** p);
     vxg_status int_column(const vxg_array& a, IntCol& c);
@@ -185,13 +182,19 @@ class Planner {
     vxg_status packed_column(const vxg_array& a, IntCol& c, bool* packed);
     vxg_status runend_column(const vxg_array& a, bool in_place, IntCol& c);
 
-    vxg_status decode_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs a, void* dst);
+    // A BitPacked array under the epilogue of its parents: validate it and describe its K1 decode
+    // (*patches: its patches child, or null), then queue the decode into `sink` or, without one,
+    // launch it (+ the patch scatter) now -- `fused`: outer patches the launch itself writes.
+    vxg_status describe_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs& a, void* dst, K1Job& j,
+                                  const vxg_array** patches);
+    vxg_status submit_k1(const K1Job& j, const vxg_array* patches, const UnpackArgs& a, K1Sink* sink, const PatchCol* fused);
+    vxg_status decode_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs a, void* dst, K1Sink* sink);
     bool patch_fusable(const vxg_array& sparse, int value_width) const;
     vxg_status sparse_patch_col(const vxg_array& sparse, PatchCol& pc);
     vxg_status apply_sparse_patches(const vxg_array& sparse, int T, Epi epi, int vw, const UnpackArgs& a,
                                     void* dst, uint64_t out_len);
-    vxg_status decode_alp(const vxg_array& a, void* dst);
-    vxg_status decode_dict_primitive(const vxg_array& a, void* dst);
+    vxg_status decode_alp(const vxg_array& a, void* dst, K1Sink* sink);
+    vxg_status decode_dict_primitive(const vxg_array& a, void* dst, K1Sink* sink);
     vxg_status decode_chunked_primitive(const vxg_array& a, void* dst);
     vxg_status decode_alprd(const vxg_array& a, void* dst);
     vxg_status decode_sparse_values(const vxg_array& a, void* dst);
@@ -229,7 +232,7 @@ class Planner {
     vxg_status string_lens(const vxg_array& a, std::vector<uint64_t>& lens,
                            std::vector<std::pair<size_t, const vxg_array*>>& fsst) const;
     vxg_status strings_into(const vxg_array& a, uint8_t* views, uint8_t* data, const vxg_data_buffer* bufs,
-                            uint32_t bidx, const uint8_t* validity);
+                            uint32_t bidx, const uint8_t* validity, std::vector<FsstChunk>* fsst_sink);
 };
 
 }  // namespace vxg

@@ -118,33 +118,41 @@ vxg_status Planner::sparse_patch_col(const vxg_array& sp, PatchCol& pc) {
     return VXG_OK;
 }
 
-vxg_status Planner::decode_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs a, void* dst) {
+vxg_status Planner::describe_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs& a, void* dst, K1Job& j,
+                                       const vxg_array** patches) {
     // bitpacking/mod.rs:215-219 -> compress.rs:167-189 (patches: child 0 when has_patches)
-    const int T = 8 * width(bp);
     if (!ptype_is_int(bp.ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "BitPacked needs an integer ptype");
     const vxg_buffer* packed = buf(bp, 0);
-    const unsigned W = bp.meta.bitpacked.bit_width;
     a.err = ctx_->c.err_word;
-    K1Job j;
-    VXG_TRY(make_k1_job(T, W, bp.meta.bitpacked.offset, bp.len, packed ? packed->ptr : nullptr,
-                        packed ? packed->len : 0, epi, vw, a, dst, j));
-    const vxg_array* p = nullptr;
-    if (bp.meta.bitpacked.has_patches) {
-        p = child(bp, 0);
-        if (!p) return set_error(VXG_ERR_INVALID_ARGUMENT, "BitPackedArray: patches child missing");
-    }
-    if (k1_batch_) {  // a chunk of a ChunkedArray: launched with the other chunks
-        k1_batch_->push_back(j);
-        if (p) patch_batch_->push_back(PatchJob{p, T, epi, vw, a, dst, bp.len});
-        return VXG_OK;
-    }
-    std::vector<K1Job> one{j};
-    VXG_TRY(launch_k1_jobs(one, ctx_->c.err_word, s_, plan_, false, nullptr, fused_patch_));
-    if (p) VXG_TRY(apply_sparse_patches(*p, T, epi, vw, a, dst, bp.len));
+    VXG_TRY(make_k1_job(8 * width(bp), bp.meta.bitpacked.bit_width, bp.meta.bitpacked.offset, bp.len,
+                        packed ? packed->ptr : nullptr, packed ? packed->len : 0, epi, vw, a, dst, j));
+    *patches = bp.meta.bitpacked.has_patches ? child(bp, 0) : nullptr;
+    if (bp.meta.bitpacked.has_patches && !*patches)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "BitPackedArray: patches child missing");
     return VXG_OK;
 }
 
-vxg_status Planner::decode_alp(const vxg_array& a, void* dst) {
+vxg_status Planner::submit_k1(const K1Job& j, const vxg_array* patches, const UnpackArgs& a, K1Sink* sink,
+                              const PatchCol* fused) {
+    if (sink) {  // a chunk of a ChunkedArray: launched with the other chunks
+        sink->jobs.push_back(j);
+        if (patches) sink->patches.push_back(PatchJob{patches, j.T, j.epi, j.vw, a, j.d.out, j.d.len});
+        return VXG_OK;
+    }
+    std::vector<K1Job> one{j};
+    VXG_TRY(launch_k1_jobs(one, ctx_->c.err_word, s_, plan_, fused));
+    if (patches) VXG_TRY(apply_sparse_patches(*patches, j.T, j.epi, j.vw, a, j.d.out, j.d.len));
+    return VXG_OK;
+}
+
+vxg_status Planner::decode_bitpacked(const vxg_array& bp, Epi epi, int vw, UnpackArgs a, void* dst, K1Sink* sink) {
+    K1Job j;
+    const vxg_array* p;
+    VXG_TRY(describe_bitpacked(bp, epi, vw, a, dst, j, &p));
+    return submit_k1(j, p, a, sink, nullptr);
+}
+
+vxg_status Planner::decode_alp(const vxg_array& a, void* dst, K1Sink* sink) {
     // alp/array.rs:269 -> alp/compress.rs:61-78 (+ patch_decoded :80-96)
     const vxg_array* enc = child(a, 0);
     if (!enc) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: encoded child missing");
@@ -170,20 +178,21 @@ vxg_status Planner::decode_alp(const vxg_array& a, void* dst) {
     if (bp && width(*bp) == (f32 ? 4 : 8)) {
         PatchCol pc{};
         const vxg_array* p = a.meta.alp.has_patches ? child(a, 1) : nullptr;
-        if (p && !k1_batch_ && !patch_batch_ && !bp->meta.bitpacked.has_patches && bp->len == a.len &&
-            patch_fusable(*p, f32 ? 4 : 8) && fused_patches_enabled()) {
+        if (p && !sink && !bp->meta.bitpacked.has_patches && bp->len == a.len && patch_fusable(*p, f32 ? 4 : 8) &&
+            fused_patches_enabled()) {
+            // the launch submit_k1 makes: one kernel-argument table of this array's blocks
             const uint64_t nblk = (bp->len + bp->meta.bitpacked.offset + 1023) / 1024;
-            if (k1_takes_wave(f32 ? 32 : 64, int(bp->meta.bitpacked.bit_width), epi, (nblk + 31) / 32)) {
+            if (k1_choose(f32 ? 32 : 64, int(bp->meta.bitpacked.bit_width), epi, false, (nblk + 31) / 32, false,
+                          k1_wave_mode(), split_below_groups()).kind == K1Kind::Wave) {
                 VXG_TRY(sparse_patch_col(*p, pc));
                 fused = !pc.idx.packed || pc.idx.W > 0;  // K1w reads 8-byte index words directly
             }
         }
-        fused_patch_ = fused ? &pc : nullptr;
-        g_k1w_wrote_patches = false;
-        const vxg_status st = decode_bitpacked(*bp, epi, 0, ua, dst);  // fused unpack+FoR+ALP (+patches)
-        fused_patch_ = nullptr;
-        VXG_TRY(st);
-        fused = fused && g_k1w_wrote_patches;  // any other K1 path left them to the scatter below
+        K1Job j;
+        const vxg_array* inner;
+        VXG_TRY(describe_bitpacked(*bp, epi, 0, ua, dst, j, &inner));
+        fused = fused && j.d.n_blocks;  // (an empty array launches nothing)
+        VXG_TRY(submit_k1(j, inner, ua, sink, fused ? &pc : nullptr));  // fused unpack+FoR+ALP (+patches)
     } else {
         const void* penc;
         VXG_TRY(view_primitive(*enc, &penc));
@@ -194,8 +203,8 @@ vxg_status Planner::decode_alp(const vxg_array& a, void* dst) {
         if (!p) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: patches child missing");
         UnpackArgs plain{};
         plain.err = ctx_->c.err_word;
-        if (patch_batch_) {  // after the chunk's K1 decode and its inner patches
-            patch_batch_->push_back(PatchJob{p, f32 ? 32 : 64, Epi::Plain, 0, plain, dst, a.len});
+        if (sink) {  // after the chunk's K1 decode and its inner patches
+            sink->patches.push_back(PatchJob{p, f32 ? 32 : 64, Epi::Plain, 0, plain, dst, a.len});
             return VXG_OK;
         }
         VXG_TRY(apply_sparse_patches(*p, f32 ? 32 : 64, Epi::Plain, 0, plain, dst, a.len));
@@ -203,7 +212,7 @@ vxg_status Planner::decode_alp(const vxg_array& a, void* dst) {
     return VXG_OK;
 }
 
-vxg_status Planner::decode_dict_primitive(const vxg_array& a, void* dst) {
+vxg_status Planner::decode_dict_primitive(const vxg_array& a, void* dst, K1Sink* sink) {
     // dict/array.rs:68-73: take(canonical(values), codes)
     const vxg_array* values = child(a, 0);
     const vxg_array* codes = child(a, 1);
@@ -217,7 +226,7 @@ vxg_status Planner::decode_dict_primitive(const vxg_array& a, void* dst) {
         UnpackArgs ua{};
         ua.dict = pv;
         ua.dict_len = values->len;
-        return decode_bitpacked(*codes, Epi::Dict, vw, ua, dst);
+        return decode_bitpacked(*codes, Epi::Dict, vw, ua, dst, sink);
     }
     const void* pc;
     VXG_TRY(view_primitive(*codes, &pc));
@@ -266,6 +275,7 @@ vxg_status Planner::decode_chunked_primitive(const vxg_array& a, void* dst) {
     const int w = width(a);
     std::vector<K1Job> jobs;
     std::vector<PatchJob> patches;
+    K1Sink sink{jobs, patches};
     std::vector<RunEndChunk> runs;
     std::vector<uint8_t> runs_indep;  // the run's children are read in place (no level-0 decode)
     // RunEnd chunks whose ends/values are primitive or one K1 decode: their temporaries
@@ -307,12 +317,7 @@ vxg_status Planner::decode_chunked_primitive(const vxg_array& a, void* dst) {
         if (x.encoding == VXG_ENC_PRIMITIVE) return view_primitive(x, p);
         *p = tmp;
         tmp += (x.len * width(x) + 15) & ~15ull;
-        k1_batch_ = &jobs;
-        patch_batch_ = &patches;
-        const vxg_status st = decode_into(x, const_cast<void*>(*p));
-        k1_batch_ = nullptr;
-        patch_batch_ = nullptr;
-        return st;
+        return decode_into(x, const_cast<void*>(*p), &sink);
     };
     uint64_t off = 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -321,12 +326,7 @@ vxg_status Planner::decode_chunked_primitive(const vxg_array& a, void* dst) {
             return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the ChunkedArray's dtype");
         uint8_t* slice = static_cast<uint8_t*>(dst) + off * w;
         if (k1_fusable(c)) {
-            k1_batch_ = &jobs;
-            patch_batch_ = &patches;
-            const vxg_status st = decode_into(c, slice);
-            k1_batch_ = nullptr;
-            patch_batch_ = nullptr;
-            VXG_TRY(st);
+            VXG_TRY(decode_into(c, slice, &sink));
         } else if (batch_runend(c)) {
             // runend/compress.rs:115-148 (runend/array.rs:191-197)
             const vxg_array& e = *child(c, 0);
@@ -365,7 +365,7 @@ vxg_status Planner::decode_chunked_primitive(const vxg_array& a, void* dst) {
         for (size_t k = 0; k < runs.size(); k++) batch_->runs.push_back(PlanBatch::Run{w, runs[k], runs_indep[k] != 0});
         return VXG_OK;
     }
-    VXG_TRY(launch_k1_jobs(jobs, ctx_->c.err_word, s_, plan_));
+    VXG_TRY(launch_k1_jobs(jobs, ctx_->c.err_word, s_, plan_, nullptr));
     for (const PatchJob& p : patches) VXG_TRY(apply_sparse_patches(*p.sp, p.T, p.epi, p.vw, p.a, p.dst, p.out_len));
     return launch_runs(runs, w, ctx_->c.err_word, s_, plan_);
 }
@@ -412,7 +412,7 @@ vxg_status Planner::decode_sparse_values(const vxg_array& a, void* dst) {
     return apply_sparse_patches(a, 8 * width(a), Epi::Plain, 0, plain, dst, a.len);
 }
 
-vxg_status Planner::decode_into(const vxg_array& a, void* dst) {
+vxg_status Planner::decode_into(const vxg_array& a, void* dst, K1Sink* sink) {
     if (!is_primitive_dtype(a)) return set_error(VXG_ERR_MISMATCHED_TYPES, "expected a primitive dtype");
     const int w = width(a);
     if (w == 0) return set_error(VXG_ERR_NOT_IMPLEMENTED, "unsupported ptype");
@@ -425,7 +425,7 @@ vxg_status Planner::decode_into(const vxg_array& a, void* dst) {
         return VXG_OK;
     }
     case VXG_ENC_FL_BITPACKED:
-        return decode_bitpacked(a, Epi::Plain, 0, UnpackArgs{}, dst);
+        return decode_bitpacked(a, Epi::Plain, 0, UnpackArgs{}, dst, sink);
     case VXG_ENC_FL_FOR: {
         // for/mod.rs:105-109 -> for/compress.rs:86-98
         const vxg_array* enc = child(a, 0);
@@ -435,7 +435,7 @@ vxg_status Planner::decode_into(const vxg_array& a, void* dst) {
             UnpackArgs ua{};
             ua.reference = a.meta.for_.reference;
             ua.shift = a.meta.for_.shift;
-            return decode_bitpacked(*enc, Epi::For, 0, ua, dst);
+            return decode_bitpacked(*enc, Epi::For, 0, ua, dst, sink);
         }
         VXG_TRY(decode_into(*enc, dst));
         return launch_for(w, dst, a.len, a.meta.for_.reference, a.meta.for_.shift, false, dst, s_);
@@ -445,16 +445,16 @@ vxg_status Planner::decode_into(const vxg_array& a, void* dst) {
         if (!enc) return set_error(VXG_ERR_INVALID_ARGUMENT, "ZigZagArray is missing encoded child");
         if (!ptype_is_signed(a.ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "ZigZag decodes to signed ints");
         if (enc->encoding == VXG_ENC_FL_BITPACKED && width(*enc) == w)
-            return decode_bitpacked(*enc, Epi::ForZigZag, 0, UnpackArgs{}, dst);
+            return decode_bitpacked(*enc, Epi::ForZigZag, 0, UnpackArgs{}, dst, sink);
         VXG_TRY(decode_into(*enc, dst));
         return launch_zigzag(w, dst, a.len, dst, s_);
     }
     case VXG_ENC_ALP:
-        return decode_alp(a, dst);
+        return decode_alp(a, dst, sink);
     case VXG_ENC_ALP_RD:
         return decode_alprd(a, dst);
     case VXG_ENC_DICT:
-        return decode_dict_primitive(a, dst);
+        return decode_dict_primitive(a, dst, sink);
     case VXG_ENC_FL_DELTA: {
         // delta/mod.rs:237 -> delta/compress.rs:100-166
         const vxg_array* bases = child(a, 0);

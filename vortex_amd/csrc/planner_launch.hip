@@ -19,8 +19,6 @@ static_assert(sizeof(vxg::CmpTable) + 32 <= 4096, "CmpTable and the compare argu
 
 namespace vxg {
 
-thread_local bool g_k1w_wrote_patches = false;
-
 void note_k1w_launch(uint32_t bpw, uint32_t bpw_max, uint64_t groups) {
     if (!g_cur_ctx) return;
     std::lock_guard<std::mutex> lk(g_cur_ctx->mu);
@@ -31,14 +29,6 @@ void note_k1w_launch(uint32_t bpw, uint32_t bpw_max, uint64_t groups) {
     st.k1w_last_bpw = bpw;
     st.k1w_last_bpw_max = bpw_max;
     st.k1w_last_groups = groups;
-}
-
-// launch_one's choice (fl_unpack_impl.hpp) for a kernel-argument table: K1w unless the launch is
-// small enough for the row split (T = 32/64) or the K1_WAVE option / VXG_K1_WAVE says otherwise.
-bool k1_takes_wave(int T, int W, Epi epi, uint64_t groups32) {
-    const int mode = k1_wave_mode();
-    const bool split = (T == 32 || T == 64) && W > 0 && groups32 < split_below_groups();
-    return groups32 > 0 && (mode == 2 || (mode == 1 && !split && epi != Epi::Dict));
 }
 
 // K1 dispatch over the instantiation units.
@@ -94,130 +84,76 @@ static int k1_out_width(int T, Epi epi, int vw) {
     return epi == Epi::Dict ? vw : (epi == Epi::AlpF32 ? 4 : (epi == Epi::AlpF64 ? 8 : T / 8));
 }
 
-// Launch K1 jobs grouped by kernel (T, W, epilogue, value width), kArgChunks chunks per launch
-// with the chunk table as the kernel argument (no device table, no upload, no host sync).
-// While a plan is recorded (dt set), a group of any size is one launch over a device table, and
-// (generic_small: a plan's batch) the groups whose output is small all share ONE K1g launch
-// (k1g.hpp): a sharded scan's many small per-column kernels cost more in ramp, drain and graph
-// edges than in data.
-vxg_status launch_k1_jobs(std::vector<K1Job>& jobs, uint32_t* err, hipStream_t s, DevTables* dt, bool generic_small,
-                          const std::vector<std::pair<int, RunEndChunk>>* gen_runs, const PatchCol* patch,
-                          const FsstFused* fuse) {
+// Sort `jobs` by kernel (T, W, epilogue, value width) and call group(i, j, out_bytes) for every
+// run [i, j) of jobs with the same kernel, at most max_group jobs long; out_bytes = its output.
+template <class Group>
+static vxg_status for_each_kernel_group(std::vector<K1Job>& jobs, size_t max_group, Group group) {
     std::stable_sort(jobs.begin(), jobs.end(), [](const K1Job& a, const K1Job& b) {
         return std::make_tuple(a.T, a.W, int(a.epi), a.vw, a.vb) < std::make_tuple(b.T, b.W, int(b.epi), b.vw, b.vb);
     });
-    std::vector<const K1Job*> gen;  // jobs for the shared K1g launch
-    // one kernel group's own launch (outside a plan the group holds at most kArgChunks jobs);
-    // empty jobs take no part
-    auto launch_group = [&](size_t i, size_t j) -> vxg_status {
-        const K1Job* it = jobs.data() + i;
-        const K1Job* const end = jobs.data() + j;
-        while (it != end) {
-            ChunkTable tab{};
-            tab.err = err;
-            if (patch && jobs.size() == 1) tab.patch = *patch;  // a single array's K1w (k1_takes_wave)
-            uint64_t groups;
-            VXG_TRY(pack_chunk_table(
-                tab, it, end, dt, [](const K1Job& jb) { return jb.d.n_blocks ? &jb.d : nullptr; },
-                [](const ChunkDev& c) { return (c.n_blocks + 31) / 32; }, &groups));
-            if (tab.n) VXG_TRY(launch_fl_unpack(jobs[i].T, jobs[i].W, jobs[i].epi, jobs[i].vw, tab, groups, s));
-        }
-        return VXG_OK;
-    };
-    size_t i = 0;
-    while (i < jobs.size()) {
-        size_t j = i;
+    for (size_t i = 0, j; i < jobs.size(); i = j) {
         uint64_t out_bytes = 0;
-        while (j < jobs.size() && (dt || j - i < size_t(kArgChunks)) && same_kernel(jobs[i], jobs[j])) {
+        for (j = i; j < jobs.size() && j - i < max_group && same_kernel(jobs[i], jobs[j]); j++)
             out_bytes += jobs[j].d.len * uint64_t(k1_out_width(jobs[j].T, jobs[j].epi, jobs[j].vw));
-            j++;
-        }
-        if (jobs[i].vb || (dt && generic_small && out_bytes < k1g_max_bytes() &&
-                           gen_kind(jobs[i].T, int(jobs[i].epi), jobs[i].vw) >= 0)) {
-            if (!dt) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin-dictionary K1 jobs need a plan");
-            for (size_t k = i; k < j; k++)
-                if (jobs[k].d.n_blocks) gen.push_back(&jobs[k]);
-            i = j;
-            continue;
-        }
-        VXG_TRY(launch_group(i, j));
-        i = j;
-    }
-    const size_t n_runs = gen_runs ? gen_runs->size() : 0;
-    if (!gen.empty() || n_runs || (fuse && fuse->valid)) {
-        if (!dt) return set_error(VXG_ERR_INVALID_ARGUMENT, "internal: K1g launch outside a plan");
-        if (gen.size() + n_runs > 0xFFFFFFFFull) return set_error(VXG_ERR_INVALID_ARGUMENT, "too many chunks");
-        GenChunk* host;
-        const GenChunk* ext;
-        VXG_TRY(dt->table(gen.size() + n_runs, &host, &ext));
-        uint64_t groups = 0;
-        bool dict_lds = true;
-        uint32_t packed_bytes = 0, dict_bytes = 0, runs_bytes = 0;
-        // a launch of string-dictionary jobs alone (an unbatched plan's chunked Dict(VarBin)
-        // column): one FastLanes block of codes per workgroup (gen_vb_bpw)
-        const bool vb_alone = n_runs == 0 && !(fuse && fuse->valid) &&
-                              std::all_of(gen.begin(), gen.end(), [](const K1Job* jp) { return jp->vb; });
-        uint64_t gen_blocks = 0;
-        for (const K1Job* jp : gen) gen_blocks += jp->d.n_blocks;
-        const uint32_t bpw_cap = gen_bpw_cap(gen_blocks);
-        for (size_t k = 0; k < gen.size(); k++) {
-            const K1Job& jb = *gen[k];
-            GenChunk& g = host[k];
-            g.d = jb.d;
-            g.kind = uint32_t(gen_kind(jb.T, int(jb.epi), jb.vw, jb.vb));
-            g.W = uint32_t(jb.W);
-            g.bpw = jb.vb ? gen_vb_bpw(jb.T, jb.W, vb_alone, bpw_cap) : gen_bpw(jb.T, jb.W, bpw_cap);
-            g.d.first_group = groups;
-            groups += (jb.d.n_blocks + g.bpw - 1) / g.bpw;
-            packed_bytes = std::max(packed_bytes, g.bpw * 128u * uint32_t(jb.W));
-            if (jb.vb) {
-                dict_bytes = std::max(dict_bytes, gen_vb_stage_bytes(jb.d.dict_len, jb.vbc.bytes));
-                g.vb_src = jb.vbc.src;
-                g.vb_offs = jb.vbc.offsets;
-                g.vb_offs_width = jb.vbc.offs_width;
-                g.vb_dst = jb.vbc.dst;
-                g.vb_bytes = jb.vbc.bytes;
-                g.vb_bidx = jb.vbc.bidx;
-            } else if (jb.epi == Epi::Dict) {
-                dict_lds = dict_lds && jb.d.dict_len * uint64_t(jb.vw) <= uint64_t(kDictLdsBytes) &&
-                           (reinterpret_cast<uintptr_t>(jb.d.dict) & 15) == 0;
-            }
-        }
-        if (dict_lds)  // every plain Dict job stages its dictionary
-            for (const K1Job* jp : gen)
-                if (jp->epi == Epi::Dict && !jp->vb)
-                    dict_bytes = std::max(dict_bytes, uint32_t((jp->d.dict_len * uint64_t(jp->vw) + 15) & ~15ull));
-        for (size_t k = 0; k < n_runs; k++) {  // short-run RunEnd expansions (runend_runs.hpp)
-            const auto& [w, r] = (*gen_runs)[k];
-            GenChunk& g = host[gen.size() + k];
-            g.kind = uint32_t(gen_runs_kind(w));
-            g.re = r;
-            g.d.first_group = groups;
-            g.d.n_blocks = r.n_runs;  // (unused by the body; keeps the entry self-describing)
-            groups += (r.n_runs + kRunEndRunsPerGroup - 1) / kRunEndRunsPerGroup;
-            runs_bytes = std::max(runs_bytes, gen_runs_lds_bytes(w));
-        }
-        std::vector<uint64_t> cnt(gen.size() + n_runs);  // workgroups per job (direct job lookup when equal)
-        for (size_t k = 0; k < cnt.size(); k++)
-            cnt[k] = (k + 1 < cnt.size() ? host[k + 1].d.first_group : groups) - host[k].d.first_group;
-        uint64_t gpe = common_groups(cnt.data(), cnt.size());
-        // Nearly equal counts (C5's RunEnd chunks: 16 or 17 workgroups; every column's last chunk
-        // smaller): every job padded to the largest count when that adds <= 1/10 idle workgroups,
-        // so a workgroup finds its job by one division instead of a wave-wide search over the
-        // table (one or more dependent round trips before its loads; gen_dispatch returns at once
-        // on a padding workgroup).
-        if (!gpe && cnt.size() > 1) {
-            const uint64_t m = *std::max_element(cnt.begin(), cnt.end());
-            if (m * cnt.size() - groups <= groups / 10) {
-                for (size_t k = 0; k < cnt.size(); k++) host[k].d.first_group = k * m;
-                groups = m * cnt.size();
-                gpe = m;
-            }
-        }
-        VXG_TRY(launch_k1_generic(ext, uint32_t(gen.size() + n_runs), groups, dict_lds, packed_bytes, dict_bytes,
-                                    runs_bytes, err, s, gpe, fuse));
+        VXG_TRY(group(i, j, out_bytes));
     }
     return VXG_OK;
+}
+
+// One kernel group's own launches: the chunk table as the kernel argument, kArgChunks jobs per
+// launch (no device table, no upload, no host sync), or -- dt set, a longer group -- one launch
+// over a device table.  Empty jobs take no part.  `patch`: the outer patches of a single array,
+// written by its K1w launch.
+static vxg_status launch_kernel_group(const K1Job* it, const K1Job* end, uint32_t* err, hipStream_t s, DevTables* dt,
+                                      const PatchCol* patch) {
+    const K1Job& k = *it;
+    while (it != end) {
+        ChunkTable tab{};
+        tab.err = err;
+        if (patch) tab.patch = *patch;
+        uint64_t groups;
+        VXG_TRY(pack_chunk_table(
+            tab, it, end, dt, [](const K1Job& jb) { return jb.d.n_blocks ? &jb.d : nullptr; },
+            [](const ChunkDev& c) { return (c.n_blocks + 31) / 32; }, &groups));
+        if (tab.n) VXG_TRY(launch_fl_unpack(k.T, k.W, k.epi, k.vw, tab, groups, s));
+    }
+    return VXG_OK;
+}
+
+static void add_nonempty(std::vector<const K1Job*>& gen, const K1Job* it, const K1Job* end) {
+    for (; it != end; ++it)
+        if (it->d.n_blocks) gen.push_back(it);
+}
+
+// Launch K1 jobs now, grouped by kernel.  While a plan is recorded (dt set) a group of any size
+// is one launch, and Dict-over-VarBin jobs (K1Job::vb, made for plans only) share one K1g launch.
+// `patch` (one job only): see launch_kernel_group.
+vxg_status launch_k1_jobs(std::vector<K1Job>& jobs, uint32_t* err, hipStream_t s, DevTables* dt, const PatchCol* patch) {
+    if (patch && jobs.size() != 1) return set_error(VXG_ERR_INVALID_ARGUMENT, "internal: fused patches need a single K1 job");
+    std::vector<const K1Job*> gen;
+    VXG_TRY(for_each_kernel_group(jobs, dt ? jobs.size() : size_t(kArgChunks), [&](size_t i, size_t j, uint64_t) -> vxg_status {
+        if (!jobs[i].vb) return launch_kernel_group(jobs.data() + i, jobs.data() + j, err, s, dt, patch);
+        if (!dt) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin-dictionary K1 jobs need a plan");
+        add_nonempty(gen, jobs.data() + i, jobs.data() + j);
+        return VXG_OK;
+    }));
+    return gen.empty() ? VXG_OK : launch_k1g_jobs(gen, {}, FsstFused{}, err, s, *dt);
+}
+
+// A plan batch's K1 jobs: one launch over a device table per large kernel group, and ONE K1g
+// launch (k1g.hpp) for all the groups whose output is small, gen_runs and the fused FSST group: a
+// sharded scan's many small per-column kernels cost more in ramp, drain and graph edges than in
+// data.
+static vxg_status launch_plan_k1_jobs(std::vector<K1Job>& jobs, const std::vector<std::pair<int, RunEndChunk>>& gen_runs,
+                                      const FsstFused& fuse, uint32_t* err, hipStream_t s, DevTables& dt) {
+    std::vector<const K1Job*> gen;  // jobs for the shared K1g launch
+    VXG_TRY(for_each_kernel_group(jobs, jobs.size(), [&](size_t i, size_t j, uint64_t out_bytes) -> vxg_status {
+        if (const K1Job& k = jobs[i]; !k.vb && (out_bytes >= k1g_max_bytes() || gen_kind(k.T, int(k.epi), k.vw) < 0))
+            return launch_kernel_group(jobs.data() + i, jobs.data() + j, err, s, &dt, nullptr);
+        add_nonempty(gen, jobs.data() + i, jobs.data() + j);
+        return VXG_OK;
+    }));
+    return launch_k1g_jobs(gen, gen_runs, fuse, err, s, dt);
 }
 
 // Validate one BitPacked buffer (bitpacking/mod.rs:54-130) and describe its K1 decode.
@@ -307,7 +243,7 @@ vxg_status flush_plan_batch(PlanBatch& b, uint32_t* err, hipStream_t s, DevTable
     FsstFused ff;
     if (!b.fssts.empty()) {
         void* scratch = nullptr;
-        VXG_TRY(hip_check(hipMalloc(&scratch, (fsst_batch_scratch_bytes(b.fssts.data(), b.fssts.size()) + 15) & ~15ull),
+        VXG_TRY(hip_check(hipMalloc(&scratch, (fsst_chunks_scratch_bytes(b.fssts.data(), b.fssts.size()) + 15) & ~15ull),
                             "hipMalloc (plan FSST scratch)"));
         dt->allocs.push_back(scratch);
         VXG_TRY(launch_fsst_batch(b.fssts, scratch, err, s, dt, plan_fuse_enabled() ? &ff : nullptr));
@@ -322,7 +258,7 @@ vxg_status flush_plan_batch(PlanBatch& b, uint32_t* err, hipStream_t s, DevTable
         if (r.indep && r.c.len <= kRunEndShortRun * r.c.n_runs && gen_runs_kind(r.w) >= 0) gen_runs.emplace_back(r.w, r.c);
         else rest.push_back(r);
     }
-    VXG_TRY(launch_k1_jobs(b.jobs, err, s, dt, true, &gen_runs, nullptr, &ff));
+    VXG_TRY(launch_plan_k1_jobs(b.jobs, gen_runs, ff, err, s, *dt));
     std::vector<int> widths;
     for (const auto& r : rest) widths.push_back(r.w);
     std::sort(widths.begin(), widths.end());

@@ -103,8 +103,10 @@ vxg_status Planner::string_layout(const vxg_array& a, std::vector<vxg_data_buffe
 
 // Canonical views of `a` into `views`, its data buffers into `data` at bufs[0..k), non-inlined
 // views carrying buffer_index bidx + (buffer within a).  `validity`: a's LSB bitmap or NULL.
+// `fsst_sink`: `a` is an FSST chunk of a chunked array, decoded with that array's other FSST
+// chunks (the chunk loop's list); null: decoded now.  Never handed on to a child.
 vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* data, const vxg_data_buffer* bufs,
-                                 uint32_t bidx, const uint8_t* validity) {
+                                 uint32_t bidx, const uint8_t* validity, std::vector<FsstChunk>* fsst_sink) {
     switch (a.encoding) {
     case VXG_ENC_VARBIN: {
         // varbin/flatten.rs:10-17: views over the whole bytes buffer (arrow-cast Utf8 -> Utf8View)
@@ -158,13 +160,13 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
         f.heap_len = bufs[0].len;
         f.views = views;
         f.bidx = bidx;
-        if (fsst_batch_) {  // a chunk: decoded with the other FSST chunks
-            fsst_batch_->push_back(f);
+        if (fsst_sink) {  // a chunk: decoded with the other FSST chunks
+            fsst_sink->push_back(f);
             return VXG_OK;
         }
         std::vector<FsstChunk> one{f};
         void* scratch;
-        VXG_TRY(temp(fsst_batch_scratch_bytes(one.data(), 1), &scratch));
+        VXG_TRY(temp(fsst_chunks_scratch_bytes(one.data(), 1), &scratch));
         return launch_fsst_batch(one, scratch, ctx_->c.err_word, s_, plan_);
     }
     case VXG_ENC_DICT: {
@@ -184,12 +186,12 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
         void* vviews;
         VXG_TRY(temp(16 * values->len, &vviews));
         VXG_TRY(strings_into(*values, static_cast<uint8_t*>(vviews), data, bufs, bidx,
-                             static_cast<const uint8_t*>(vbits)));
+                             static_cast<const uint8_t*>(vbits), nullptr));
         if (codes->encoding == VXG_ENC_FL_BITPACKED && codes->meta.bitpacked.bit_width <= kDictFusedMaxW) {
             UnpackArgs ua{};
             ua.dict = vviews;
             ua.dict_len = values->len;
-            return decode_bitpacked(*codes, Epi::Dict, 16, ua, views);
+            return decode_bitpacked(*codes, Epi::Dict, 16, ua, views, nullptr);
         }
         const void* pc;
         VXG_TRY(view_primitive(*codes, &pc));
@@ -224,6 +226,7 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
         std::vector<VarBinChunk> dicts;
         std::vector<K1Job> jobs;
         std::vector<PatchJob> patches;
+        K1Sink sink{jobs, patches};
         std::vector<FsstChunk> fssts;
         uint64_t row = 0;
         uint32_t b = 0;
@@ -258,19 +261,12 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
                 ua.dict = vb ? nullptr : dviews;
                 ua.dict_len = v.len;
                 dviews += 16 * v.len;
-                k1_batch_ = &jobs;
-                patch_batch_ = &patches;
-                const size_t nj = jobs.size(), np = patches.size();
-                const vxg_status st = decode_bitpacked(c.children[1], Epi::Dict, 16, ua, views + 16 * row);
-                k1_batch_ = nullptr;
-                patch_batch_ = nullptr;
-                VXG_TRY(st);
-                if (vb) {
-                    if (jobs.size() != nj + 1 || patches.size() != np)
-                        return set_error(VXG_ERR_INVALID_ARGUMENT, "internal: VarBin-dictionary job shape");
-                    jobs.back().vb = true;
-                    jobs.back().vbc = d;
-                }
+                K1Job j;
+                const vxg_array* p;  // (null with vb)
+                VXG_TRY(describe_bitpacked(codes, Epi::Dict, 16, ua, views + 16 * row, j, &p));
+                j.vb = vb;
+                if (vb) j.vbc = d;
+                VXG_TRY(submit_k1(j, p, ua, &sink, nullptr));
             } else {
                 void* cv = nullptr;  // the chunk's own validity (null views are all-zero)
                 const vxg_array* vn;
@@ -280,11 +276,8 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
                     VXG_TRY(temp(((c.len + 31) / 32) * 4, &cv));
                     VXG_TRY(validity_into(c, &cv));
                 }
-                if (c.encoding == VXG_ENC_FSST) fsst_batch_ = &fssts;
-                const vxg_status st =
-                    strings_into(c, views + 16 * row, data, bufs + b, bidx + b, static_cast<const uint8_t*>(cv));
-                fsst_batch_ = nullptr;
-                VXG_TRY(st);
+                VXG_TRY(strings_into(c, views + 16 * row, data, bufs + b, bidx + b, static_cast<const uint8_t*>(cv),
+                                     c.encoding == VXG_ENC_FSST ? &fssts : nullptr));
             }
             row += c.len;
             b += k;
@@ -294,7 +287,7 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
             batch_->fssts.insert(batch_->fssts.end(), fssts.begin(), fssts.end());
         } else if (!fssts.empty()) {
             void* scratch;
-            VXG_TRY(temp(fsst_batch_scratch_bytes(fssts.data(), fssts.size()), &scratch));
+            VXG_TRY(temp(fsst_chunks_scratch_bytes(fssts.data(), fssts.size()), &scratch));
             VXG_TRY(launch_fsst_batch(fssts, scratch, ctx_->c.err_word, s_, plan_));
         }
         if (defer(a) && patches.empty()) {  // a plan's root: launched with the other arrays' jobs (PlanBatch)
@@ -303,7 +296,7 @@ vxg_status Planner::strings_into(const vxg_array& a, uint8_t* views, uint8_t* da
             return VXG_OK;
         }
         VXG_TRY(launch_varbin_dicts(dicts, ctx_->c.err_word, s_, plan_));
-        VXG_TRY(launch_k1_jobs(jobs, ctx_->c.err_word, s_, plan_));
+        VXG_TRY(launch_k1_jobs(jobs, ctx_->c.err_word, s_, plan_, nullptr));
         for (const PatchJob& p : patches) VXG_TRY(apply_sparse_patches(*p.sp, p.T, p.epi, p.vw, p.a, p.dst, p.out_len));
         return VXG_OK;
     }
@@ -344,7 +337,7 @@ vxg_status Planner::string_canonical(const vxg_array& a, vxg_canonical& out) {
         std::copy(bufs.begin(), bufs.end(), out.data_buffers);
     VXG_TRY(validity_into(a, &out.validity));
     return strings_into(a, static_cast<uint8_t*>(out.views), static_cast<uint8_t*>(out.data), bufs.data(), 0,
-                        static_cast<const uint8_t*>(out.validity));
+                        static_cast<const uint8_t*>(out.validity), nullptr);
 }
 
 }  // namespace vxg

@@ -306,11 +306,6 @@ struct ChunkTable {
     uint32_t bpw;        // K1w: blocks per workgroup of this launch (0 = the width's maximum)
 };
 
-// Set (host side) by a kernel-argument K1w launch that was handed tab.patch, the only K1 path
-// that writes patches; a caller that offered patches clears it first and runs the separate
-// scatter when it stays false (no other path may silently drop them).
-extern thread_local bool g_k1w_wrote_patches;
-
 // A launch with fewer 32-block workgroups than this uses the row split (S = 4): default 1024
 // (round 5: the C3 8-GPU shard's 32-chunk kernel-argument launch is exactly 512 workgroups of 32
 // blocks, one per two CUs' worth of waves); VXG_SPLIT_BELOW overrides (read once).
@@ -318,8 +313,34 @@ inline uint64_t split_below_groups() {
     static const uint64_t v = env_u64("VXG_SPLIT_BELOW", 1024);
     return v;
 }
-// Whether launch_fl_unpack takes K1w for a kernel-argument table of `groups32` 32-block workgroups.
-bool k1_takes_wave(int T, int W, Epi epi, uint64_t groups32);
+
+// Which K1 kernel one launch takes: the ONE rule, for launch_one (fl_unpack_impl.hpp), which
+// switches on it, and for whoever must know the answer before the launch (decode_alp hands its
+// outer patches to the launch only when it will be the kernel-argument K1w, the only K1 kernel
+// that writes tab.patch).
+enum class K1Kind { None, Reg, RegSplit, Wave };  // nothing to launch; register-resident K1 with S = 1 / 4; K1w
+struct K1Choice { K1Kind kind; bool lds; };  // lds (Dict): the dictionaries are staged in LDS
+// is_ext: the table is a plan's device table; groups32: its workgroups at 32 blocks per workgroup;
+// lds_ok: every dictionary fits the LDS stage, 16-byte aligned (Dict only); mode: k1_wave_mode();
+// split_below: split_below_groups().
+inline K1Choice k1_choose(int T, int W, Epi epi, bool is_ext, uint64_t groups32, bool lds_ok, int mode,
+                          uint64_t split_below) {
+    if (groups32 == 0) return {K1Kind::None, false};
+    const bool can_split = (T == 32 || T == 64) && W > 0;
+    const bool split = can_split && groups32 < split_below;
+    // Dict gathers keep the register-resident K1 by default: C3 (u64 codes W=10, 8-byte values,
+    // dictionary in LDS) measured 0.65 of 8 TB/s with K1w against 0.70 with the row split
+    // Device-table launches (a plan's chunked columns) take K1w from kExtWaveGroups workgroups of
+    // 32 blocks: C5's 48 MB numeric columns (183) measured C5 0.52 -> 0.556 of 8 TB/s with K1w
+    // instead of the row split (sessions r04kw, r04c), but the 2-GPU shard's halves (92) 0.506 ->
+    // 0.429 (too few K1w workgroups for 256 CUs)
+    constexpr uint64_t kExtWaveGroups = 128;
+    const bool big = !split || (is_ext && groups32 >= kExtWaveGroups);
+    const bool lds = epi == Epi::Dict && lds_ok;
+    if (mode == 2 || (mode == 1 && big && epi != Epi::Dict)) return {K1Kind::Wave, lds};  // large launches: K1w
+    // a device table keeps the row split at any size where the width has one
+    return {(is_ext ? can_split : split) ? K1Kind::RegSplit : K1Kind::Reg, lds};
+}
 
 // Patch scatter with the same epilogue applied to the patch value.
 vxg_status launch_patch(int val_width, const IntCol& indices, Epi epi, int T, void* out, uint64_t out_len,
@@ -451,7 +472,7 @@ struct FsstTable {
 };
 // Scratch for a set of chunks (tile prefixes + scan-block totals + tile code ends).
 uint64_t fsst_scratch_bytes(uint64_t n);
-uint64_t fsst_batch_scratch_bytes(const FsstChunk* chunks, size_t n_chunks);
+uint64_t fsst_chunks_scratch_bytes(const FsstChunk* chunks, size_t n_chunks);
 // A batched plan's FSST group whose decode tiles run inside the plan's K1g launch
 // (fsst_k1g_kernel, launch_fsst_k1g in k1g.hpp): its device table, pre-pass records and tile map.
 struct FsstFusedArgs {
@@ -482,7 +503,7 @@ struct FsstFused {
 };
 // Decode every chunk: grouped by accessor kinds, kFsstArgChunks per launch pair (pre-pass +
 // decode; a recorded plan's group over a device table is one pair).  `scratch` >=
-// fsst_batch_scratch_bytes.  With `fuse` (recording a batched plan), one group whose accessors
+// fsst_chunks_scratch_bytes.  With `fuse` (recording a batched plan), one group whose accessors
 // the fused kernel covers gets only its pre-pass launched and is described in *fuse instead.
 // The FSST decode's diagnostics mask (VXG_FSST_ABL, read once per process) into its __constant__;
 // called by vxg_open.
