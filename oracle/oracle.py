@@ -34,6 +34,8 @@ _SIG = {
     "vxo_alp_decode_f64": (None, [VP, SZ, UINT, UINT, VP]),
     "vxo_alprd_decode_f32": (None, [VP, VP, UINT, VP, SZ, VP, VP, SZ, VP]),
     "vxo_alprd_decode_f64": (None, [VP, VP, UINT, VP, SZ, VP, VP, SZ, VP]),
+    "vxo_alprd_decode_checked_f32": (INT, [VP, VP, UINT, UINT, VP, SZ, VP, VP, SZ, VP]),
+    "vxo_alprd_decode_checked_f64": (INT, [VP, VP, UINT, UINT, VP, SZ, VP, VP, SZ, VP]),
     "vxo_take": (INT, [INT, VP, SZ, INT, VP, SZ, VP]),
     "vxo_runend_decode": (INT, [INT, VP, INT, VP, SZ, SZ, SZ, VP]),
     "vxo_runend_bool_decode": (INT, [INT, VP, SZ, SZ, INT, SZ, VP]),

@@ -330,24 +330,46 @@ void vxo_alp_decode_f64(const int64_t* enc, size_t n, unsigned e, unsigned f, do
     }
 }
 
-/* alp_rd/mod.rs:260-301 */
+/* alp_rd/mod.rs:260-301.  `dict[*code as usize]` (:287) and `left_parts_decoded[*pos as usize]`
+ * (:292) are bounds-checked indexings: a left code >= dict_len or an exception position >= n
+ * panics in the reference, so both return -1 here (nothing past either array is read or written). */
 #define ALPRD_BODY(UT)                                                                       \
-    for (size_t i = 0; i < n; i++) out_bits[i] = (UT)dict[left[i]];                          \
-    for (size_t i = 0; i < n_exc; i++) out_bits[exc_pos[i]] = (UT)exc[i];                    \
-    for (size_t i = 0; i < n; i++) out_bits[i] = (UT)((out_bits[i] << right_bw) | right[i]);
+    for (size_t i = 0; i < n; i++) {                                                         \
+        if (left[i] >= dict_len) return -1;                                                  \
+        out_bits[i] = (UT)dict[left[i]];                                                     \
+    }                                                                                        \
+    for (size_t i = 0; i < n_exc; i++) {                                                     \
+        if (exc_pos[i] >= n) return -1;                                                      \
+        out_bits[exc_pos[i]] = (UT)exc[i];                                                   \
+    }                                                                                        \
+    for (size_t i = 0; i < n; i++) out_bits[i] = (UT)((out_bits[i] << right_bw) | right[i]); \
+    return 0;
 
+int vxo_alprd_decode_checked_f32(const uint16_t* left, const uint16_t* dict, unsigned dict_len,
+                                 unsigned right_bw, const uint32_t* right, size_t n,
+                                 const uint64_t* exc_pos, const uint16_t* exc, size_t n_exc, float* out) {
+    uint32_t* out_bits = (uint32_t*)out;
+    ALPRD_BODY(uint32_t)
+}
+
+int vxo_alprd_decode_checked_f64(const uint16_t* left, const uint16_t* dict, unsigned dict_len,
+                                 unsigned right_bw, const uint64_t* right, size_t n,
+                                 const uint64_t* exc_pos, const uint16_t* exc, size_t n_exc, double* out) {
+    uint64_t* out_bits = (uint64_t*)out;
+    ALPRD_BODY(uint64_t)
+}
+
+/* The forms without a dictionary length: the caller vouches that every left code is inside dict. */
 void vxo_alprd_decode_f32(const uint16_t* left, const uint16_t* dict, unsigned right_bw,
                           const uint32_t* right, size_t n, const uint64_t* exc_pos,
                           const uint16_t* exc, size_t n_exc, float* out) {
-    uint32_t* out_bits = (uint32_t*)out;
-    ALPRD_BODY(uint32_t)
+    (void)vxo_alprd_decode_checked_f32(left, dict, 65536u, right_bw, right, n, exc_pos, exc, n_exc, out);
 }
 
 void vxo_alprd_decode_f64(const uint16_t* left, const uint16_t* dict, unsigned right_bw,
                           const uint64_t* right, size_t n, const uint64_t* exc_pos,
                           const uint16_t* exc, size_t n_exc, double* out) {
-    uint64_t* out_bits = (uint64_t*)out;
-    ALPRD_BODY(uint64_t)
+    (void)vxo_alprd_decode_checked_f64(left, dict, 65536u, right_bw, right, n, exc_pos, exc, n_exc, out);
 }
 
 /* ======================================================================================

@@ -85,6 +85,14 @@ void vxo_alprd_decode_f32(const uint16_t* left, const uint16_t* dict, unsigned r
 void vxo_alprd_decode_f64(const uint16_t* left, const uint16_t* dict, unsigned right_bw,
                           const uint64_t* right, size_t n, const uint64_t* exc_pos,
                           const uint16_t* exc, size_t n_exc, double* out);
+/* The same with the dictionary's length (dict_len entries).  Returns -1 where the reference's
+ * indexing panics: a left code >= dict_len (:287) or an exception position >= n (:292). */
+int vxo_alprd_decode_checked_f32(const uint16_t* left, const uint16_t* dict, unsigned dict_len,
+                                 unsigned right_bw, const uint32_t* right, size_t n,
+                                 const uint64_t* exc_pos, const uint16_t* exc, size_t n_exc, float* out);
+int vxo_alprd_decode_checked_f64(const uint16_t* left, const uint16_t* dict, unsigned dict_len,
+                                 unsigned right_bw, const uint64_t* right, size_t n,
+                                 const uint64_t* exc_pos, const uint16_t* exc, size_t n_exc, double* out);
 
 /* ---- Dict / take ----------------------------------------------------------------------- */
 /* dict/array.rs:68-73 -> compute/take.rs:10-34 -> primitive/compute/take.rs:58-67.

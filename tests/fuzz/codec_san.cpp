@@ -154,9 +154,9 @@ void alp_roundtrip(Rng& r, unsigned long long it) {
         ne = vxe_alprd_encode_f32(v.data(), n, &rbw, dict, &dlen, left.data(), right.data(), epos.data(), exc.data(), n + 1);
     CHECK(dlen <= 8, "ALP-RD dictionary <= 8");
     if constexpr (sizeof(F) == 8)
-        vxo_alprd_decode_f64(left.data(), dict, rbw, right.data(), n, epos.data(), exc.data(), ne, out.data());
+        CHECK(vxo_alprd_decode_checked_f64(left.data(), dict, dlen, rbw, right.data(), n, epos.data(), exc.data(), ne, out.data()) == 0, "ALP-RD decode");
     else
-        vxo_alprd_decode_f32(left.data(), dict, rbw, right.data(), n, epos.data(), exc.data(), ne, out.data());
+        CHECK(vxo_alprd_decode_checked_f32(left.data(), dict, dlen, rbw, right.data(), n, epos.data(), exc.data(), ne, out.data()) == 0, "ALP-RD decode");
     CHECK(std::memcmp(out.data(), v.data(), size_t(n) * sizeof(F)) == 0, "ALP-RD round trip (bits)");
 }
 

@@ -157,8 +157,10 @@ def canon(a: Array):
             pos = (canon(sp.children[0])[0].astype(np.int64) - sp.meta["indices_offset"]).astype(np.uint64)
             exc = np.ascontiguousarray(canon(sp.children[1])[0]).astype(np.uint16)
         out = np.zeros(a.len, dtype=dt)
-        fn = L.vxo_alprd_decode_f32 if a.ptype == "f32" else L.vxo_alprd_decode_f64
-        fn(O.p(left), O.p(d), a.meta["right_bit_width"], O.p(right), a.len, O.p(pos), O.p(exc), pos.size, O.p(out))
+        fn = L.vxo_alprd_decode_checked_f32 if a.ptype == "f32" else L.vxo_alprd_decode_checked_f64
+        if fn(O.p(left), O.p(d), d.size, a.meta["right_bit_width"], O.p(right), a.len, O.p(pos), O.p(exc), pos.size,
+              O.p(out)):
+            raise IndexError("ALP-RD left code or exception position out of bounds")
         return out, val
     if e == ENC["DICT"]:
         values = np.ascontiguousarray(canon(a.children[0])[0])

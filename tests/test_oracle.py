@@ -304,6 +304,28 @@ def test_alprd_roundtrip(ptype):
     assert got.tobytes() == vals.tobytes()
 
 
+def test_alprd_out_of_range_code_or_position_is_an_error():
+    """alp_rd/mod.rs:287 `dict[*code as usize]` and :292 `left_parts_decoded[*pos as usize]` are
+    bounds-checked: a left code >= dict_len or an exception position >= n is an error (-1), not a
+    read or write past the array."""
+    def decode(left, d, right, pos, exc):
+        out = np.zeros(left.size, dtype=np.float32)
+        rc = O.lib().vxo_alprd_decode_checked_f32(O.p(left), O.p(d), d.size, 16, O.p(right), left.size, O.p(pos), O.p(exc),
+                                          pos.size, O.p(out))
+        return rc, out.view(np.uint32).tolist()
+
+    left = np.array([0, 1, 2], np.uint16)
+    d = np.array([7, 9], np.uint16)
+    right = np.array([1, 2, 3], np.uint32)
+    none64, none16 = np.zeros(0, np.uint64), np.zeros(0, np.uint16)
+    assert decode(left, d, right, none64, none16)[0] == -1
+    left[2] = 1
+    assert decode(left, d, right, none64, none16) == (0, [(7 << 16) | 1, (9 << 16) | 2, (9 << 16) | 3])
+    assert decode(left, d, right, np.array([3], np.uint64), np.array([5], np.uint16))[0] == -1
+    rc, out = decode(left, d, right, np.array([2], np.uint64), np.array([5], np.uint16))
+    assert rc == 0 and out[2] == (5 << 16) | 3
+
+
 def test_dict_bitpacked_roundtrip():
     rng = np.random.default_rng(1)
     dv = rng.integers(0, 2 ** 63, 300, dtype=np.uint64)

@@ -80,9 +80,17 @@ using namespace vxg;
 // ===================================================================================
 // C ABI
 // ===================================================================================
+// A value width a gather / broadcast kernel is instantiated for (16 = BinaryView rows).
+static bool value_width_ok(unsigned vw) { return vw == 1 || vw == 2 || vw == 4 || vw == 8 || vw == 16; }
+
+static const char* const kShiftRange = "FoR shift out of range";
+
 static vxg_status bitunpack_common(vxg_ctx* ctx, int T, unsigned W, unsigned offset, uint64_t len,
                                    const void* packed, uint64_t packed_bytes, Epi epi, int vw,
                                    UnpackArgs a, void* out, void* stream) {
+    if (a.shift >= unsigned(T)) return set_error(VXG_ERR_INVALID_ARGUMENT, kShiftRange);
+    if (len && (!out || (W > 0 && !packed) || (epi == Epi::Dict && a.dict_len && !a.dict)))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "null packed/dict/out");
     std::vector<K1Job> jobs(1);
     VXG_TRY(make_k1_job(T, W, offset, len, packed, packed_bytes, epi, vw, a, out, jobs[0]));
     return launch_k1_jobs(jobs, ctx->c.err_word, S(stream), nullptr, nullptr);
@@ -311,6 +319,7 @@ vxg_status vxg_bitunpack_dict(vxg_ctx* ctx, int codes_ptype, unsigned bit_width,
                               uint64_t dict_len, unsigned value_width, void* out, void* stream) {
     VXG_TRY(use_device(ctx));
     if (!ptype_is_unsigned(codes_ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "Dict codes must be unsigned");
+    if (!value_width_ok(value_width)) return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");
     if (bit_width > unsigned(kDictFusedMaxW))
         return set_error(VXG_ERR_NOT_IMPLEMENTED, "fused dict decode supports code widths <= 16");
     UnpackArgs a{};
@@ -324,13 +333,17 @@ vxg_status vxg_bitunpack_dict_chunks(vxg_ctx* ctx, int codes_ptype, unsigned bit
                                      const vxg_dict_chunk* chunks_host, uint32_t n_chunks, void* stream) {
     VXG_TRY(use_device(ctx));
     if (!ptype_is_unsigned(codes_ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "Dict codes must be unsigned");
+    if (!value_width_ok(value_width)) return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");
     if (bit_width > unsigned(kDictFusedMaxW))
         return set_error(VXG_ERR_NOT_IMPLEMENTED, "fused dict decode supports code widths <= 16");
+    if (n_chunks && !chunks_host) return set_error(VXG_ERR_INVALID_ARGUMENT, "null chunk table");
     std::vector<K1Job> jobs(n_chunks);
     for (uint32_t i = 0; i < n_chunks; i++) {
         const vxg_dict_chunk& c = chunks_host[i];
         if (c.n_blocks != (c.len + 1023) / 1024)
             return set_error(VXG_ERR_INVALID_ARGUMENT, "chunk n_blocks != ceil(len/1024)");
+        if (c.len && (!c.out || (bit_width > 0 && !c.packed) || (c.dict_len && !c.dict_values)))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "null packed/dict/out in a chunk");
         UnpackArgs a{};
         a.dict = c.dict_values;
         a.dict_len = c.dict_len;
@@ -345,6 +358,7 @@ vxg_status vxg_patch(vxg_ctx* ctx, int ptype, void* out, uint64_t out_len, int i
     VXG_TRY(use_device(ctx));
     const int w = ptype_width(ptype);
     if (!w || !ptype_is_int(indices_ptype)) return set_error(VXG_ERR_INVALID_ARGUMENT, "bad ptype");
+    if (n_patches && (!out || !indices || !values)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null out/indices/values");
     UnpackArgs a{};
     a.err = ctx->c.err_word;
     IntCol ic{};
@@ -358,12 +372,15 @@ vxg_status vxg_for_decode(vxg_ctx* ctx, int ptype, const void* in, uint64_t n, u
                           unsigned shift, void* out, void* stream) {
     VXG_TRY(use_device(ctx));
     if (!ptype_is_int(ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "FoR needs an integer ptype");
+    if (shift >= unsigned(8 * ptype_width(ptype))) return set_error(VXG_ERR_INVALID_ARGUMENT, kShiftRange);
+    if (n && (!in || !out)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null in/out");
     return launch_for(ptype_width(ptype), in, n, reference, shift, false, out, S(stream));
 }
 
 vxg_status vxg_zigzag_decode(vxg_ctx* ctx, int out_ptype, const void* in, uint64_t n, void* out, void* stream) {
     VXG_TRY(use_device(ctx));
     if (!ptype_is_signed(out_ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "ZigZag decodes to signed ints");
+    if (n && (!in || !out)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null in/out");
     return launch_zigzag(ptype_width(out_ptype), in, n, out, S(stream));
 }
 
@@ -371,8 +388,10 @@ vxg_status vxg_alp_decode(vxg_ctx* ctx, int float_ptype, const void* encoded, ui
                           void* out, void* stream) {
     VXG_TRY(use_device(ctx));
     const bool f32 = float_ptype == VXG_F32;
+    if (!f32 && float_ptype != VXG_F64) return set_error(VXG_ERR_MISMATCHED_TYPES, "ALP decodes to f32 or f64 only");
     if ((f32 && (e > 10 || f > 10)) || (!f32 && (e > 23 || f > 23)))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "ALP exponents out of range");
+    if (n && (!encoded || !out)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null encoded/out");
     return launch_alp(float_ptype, encoded, n, f32 ? double(kF10f[f]) : kF10d[f],
                       f32 ? double(kIF10f[e]) : kIF10d[e], out, S(stream));
 }
@@ -382,7 +401,13 @@ vxg_status vxg_alprd_decode(vxg_ctx* ctx, int float_ptype, const uint16_t* left_
                             const uint64_t* exc_pos, const uint16_t* exc_vals, uint64_t n_exc, void* out,
                             void* stream) {
     VXG_TRY(use_device(ctx));
+    if (float_ptype != VXG_F32 && float_ptype != VXG_F64)
+        return set_error(VXG_ERR_MISMATCHED_TYPES, "ALP-RD decodes to f32 or f64 only");
     if (dict_len > 8) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALP-RD dictionary holds at most 8 entries");
+    if (right_bw == 0 || right_bw >= (float_ptype == VXG_F32 ? 32u : 64u))  // the left part is shifted by it
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "ALP-RD right bit width (shift) out of range");
+    if ((dict_len && !dict_host) || (n && (!left_codes || !right || !out)) || (n_exc && (!exc_pos || !exc_vals)))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "null dict/left/right/exceptions/out");
     return launch_alprd(float_ptype, left_codes, dict_host, dict_len, right_bw, right, n, exc_pos, 8, false, 0,
                         exc_vals, n_exc, out, ctx->c.err_word, S(stream));
 }
@@ -391,6 +416,8 @@ vxg_status vxg_take(vxg_ctx* ctx, unsigned value_width, const void* values, uint
                     const void* codes, uint64_t n, void* out, void* stream) {
     VXG_TRY(use_device(ctx));
     if (!ptype_is_unsigned(codes_ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "take indices must be unsigned");
+    if (!value_width_ok(value_width)) return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");
+    if (n && (!codes || !out || (n_values && !values))) return set_error(VXG_ERR_INVALID_ARGUMENT, "null values/codes/out");
     return launch_take(int(value_width), values, n_values, ptype_width(codes_ptype), ptype_is_signed(codes_ptype), codes, n, out,
                        ctx->c.err_word, S(stream));
 }
@@ -403,7 +430,9 @@ vxg_status vxg_delta_decode(vxg_ctx* ctx, int ptype, const void* bases, uint64_t
     const uint64_t lanes = 1024 / (8 * w);
     if (n_bases != (n_deltas / 1024) * lanes + (n_deltas % 1024 ? 1 : 0))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "DeltaArray: bases.len() != expected_bases_len");
-    if (offset + len > n_deltas) return set_error(VXG_ERR_INVALID_ARGUMENT, "offset + len > deltas len");
+    if (offset > n_deltas || len > n_deltas - offset) return set_error(VXG_ERR_INVALID_ARGUMENT, "offset + len > deltas len");
+    if (len == 0) return VXG_OK;
+    if (!bases || !deltas || !out) return set_error(VXG_ERR_INVALID_ARGUMENT, "null bases/deltas/out");
     return launch_delta(w, bases, deltas, n_deltas, offset, len, out, S(stream));
 }
 
@@ -412,6 +441,8 @@ vxg_status vxg_runend_decode(vxg_ctx* ctx, unsigned value_width, const void* val
                              void* stream) {
     VXG_TRY(use_device(ctx));
     if (!ptype_is_int(ends_ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "RunEnd ends must be integers");
+    if (!value_width_ok(value_width)) return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");
+    if (len && n_runs && (!values || !ends || !out)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null values/ends/out");
     RunEndChunk c{};
     c.ends.p = ends;
     c.ends.width = ptype_width(ends_ptype);
@@ -591,7 +622,7 @@ vxg_status vxg_runend_bool_decode(vxg_ctx* ctx, int ends_ptype, const void* ends
     VXG_TRY(use_device(ctx));
     if (!ptype_is_unsigned(ends_ptype))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "Ends array must be an unsigned integer type");
-    if (len && !out_bits) return set_error(VXG_ERR_INVALID_ARGUMENT, "null output");
+    if (len && (!out_bits || (n_runs && !ends))) return set_error(VXG_ERR_INVALID_ARGUMENT, "null ends/output");
     return launch_runend_bool(ends, ptype_width(ends_ptype), n_runs, offset, start != 0, len, out_bits,
                               out_bit_offset, ctx->c.err_word, S(stream));
 }
@@ -612,6 +643,10 @@ vxg_status vxg_fsst_decode(vxg_ctx* ctx, const uint64_t* symbols, const uint8_t*
     VXG_TRY(use_device(ctx));
     if (!ptype_is_int(offs_ptype) || !ptype_is_int(lens_ptype))
         return set_error(VXG_ERR_MISMATCHED_TYPES, "FSST offsets/lengths must be integers");
+    if (n_symbols > 255) return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbol table > 255 entries");
+    // (code_bytes and heap may be null when every string is empty: no byte of either is touched)
+    if ((n_symbols && (!symbols || !sym_lens)) || (n && (!code_offsets || !lens || !scratch || !views)))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "null symbols/offsets/lengths/scratch/views");
     FsstChunk f{};
     f.symbols = symbols;
     f.sym_lens = sym_lens;
@@ -635,7 +670,9 @@ vxg_status vxg_fill(vxg_ctx* ctx, unsigned value_width, const void* scalar_host,
                     void* stream) {
     VXG_TRY(use_device(ctx));
     uint8_t sc[16] = {0};
-    if (value_width > 16) return set_error(VXG_ERR_INVALID_ARGUMENT, "value width > 16");
+    if (!value_width_ok(value_width)) return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");
+    if (n == 0) return VXG_OK;
+    if (!scalar_host || !out) return set_error(VXG_ERR_INVALID_ARGUMENT, "null scalar/out");
     std::memcpy(sc, scalar_host, value_width);
     return launch_fill(int(value_width), sc, n, out, S(stream));
 }

@@ -281,10 +281,12 @@ template <typename UT>
 __global__ __launch_bounds__(kBlock) void alprd_kernel(const uint16_t* __restrict__ left, RdDict dict,
                                                        unsigned dict_len, unsigned rbw,
                                                        const UT* __restrict__ right, uint64_t n,
-                                                       UT* __restrict__ out) {
+                                                       UT* __restrict__ out, uint32_t* err) {
     const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
     for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
         unsigned c = left[i];
+        // dict[*code as usize] (alp_rd/mod.rs:287) panics on a code >= dict_len: OutOfBounds, left part 0
+        if (c >= dict_len) __hip_atomic_fetch_or(err, kErrTakeOOB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const UT l = UT(c < dict_len ? dict.d[c] : 0);
         out[i] = UT((l << rbw) | right[i]);
     }
@@ -312,13 +314,13 @@ vxg_status launch_alprd(int float_ptype, const uint16_t* left, const uint16_t* d
     for (unsigned i = 0; i < dict_len && i < 8; i++) d.d[i] = dict[i];
     if (float_ptype == VXG_F32) {
         if (n) hipLaunchKernelGGL((alprd_kernel<uint32_t>), dim3(grid_for(n)), dim3(kBlock), 0, s, left, d,
-                                  dict_len, rbw, static_cast<const uint32_t*>(right), n, static_cast<uint32_t*>(out));
+                                  dict_len, rbw, static_cast<const uint32_t*>(right), n, static_cast<uint32_t*>(out), err);
         if (n_exc) hipLaunchKernelGGL((alprd_exc_kernel<uint32_t>), dim3(grid_for(n_exc)), dim3(kBlock), 0, s,
                                       exc_pos, pos_width, int(pos_signed), pos_off, exc, n_exc, rbw,
                                       static_cast<const uint32_t*>(right), n, static_cast<uint32_t*>(out), err);
     } else if (float_ptype == VXG_F64) {
         if (n) hipLaunchKernelGGL((alprd_kernel<uint64_t>), dim3(grid_for(n)), dim3(kBlock), 0, s, left, d,
-                                  dict_len, rbw, static_cast<const uint64_t*>(right), n, static_cast<uint64_t*>(out));
+                                  dict_len, rbw, static_cast<const uint64_t*>(right), n, static_cast<uint64_t*>(out), err);
         if (n_exc) hipLaunchKernelGGL((alprd_exc_kernel<uint64_t>), dim3(grid_for(n_exc)), dim3(kBlock), 0, s,
                                       exc_pos, pos_width, int(pos_signed), pos_off, exc, n_exc, rbw,
                                       static_cast<const uint64_t*>(right), n, static_cast<uint64_t*>(out), err);

@@ -167,7 +167,10 @@ vxg_status make_k1_job(int T, unsigned W, unsigned offset, uint64_t len, const v
                                                        " packed bytes, got " + std::to_string(packed_bytes));
     if (W > 0 && (reinterpret_cast<uintptr_t>(packed) & 15))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "packed buffer must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(out) % uint64_t(k1_out_width(T, epi, vw)))
+    const int ow = k1_out_width(T, epi, vw);
+    if (ow != 1 && ow != 2 && ow != 4 && ow != 8 && ow != 16)  // (a Dict value width of 0 would divide by zero below)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");
+    if (reinterpret_cast<uintptr_t>(out) % uint64_t(ow))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "output buffer must be aligned to the value width");
     if (epi == Epi::Dict && W > unsigned(kDictFusedMaxW)) return VXG_ERR_NOT_IMPLEMENTED;
     // every code is out of bounds of an empty dictionary (whose buffer may be null)
