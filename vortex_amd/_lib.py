@@ -175,6 +175,14 @@ class VxgCompareBytesInfo(C.Structure):
                 ("direct_launches", C.c_uint32), ("direct_chunks", C.c_uint32), ("fallback_arrays", C.c_uint32)]
 
 
+class VxgTakeInfo(C.Structure):
+    _fields_ = [("packed_launches", C.c_uint32), ("dict_arrays", C.c_uint32), ("direct_arrays", C.c_uint32),
+                ("fallback_arrays", C.c_uint32)]
+
+
+TAKE_CANONICALIZE = 1  # VXG_TAKE_CANONICALIZE
+
+
 class VxgIntStats(C.Structure):
     _fields_ = [("n", C.c_uint64), ("min_bits", C.c_uint64), ("max_bits", C.c_uint64), ("trailing_zeros", C.c_uint32),
                 ("reserved", C.c_uint32), ("bit_width_freq", C.c_uint64 * 65)]
@@ -234,6 +242,7 @@ GPU_SIGNATURES = {
     "vxg_runend_bool_decode": (ST, [VP, INT, VP, U64, U64, INT, U64, VP, U64, VP]),
     "vxg_bytebool_to_bits": (ST, [VP, VP, U64, VP, U64, VP]),
     "vxg_take_array": (ST, [VP, VP, INT, VP, U64, VP, VP]),
+    "vxg_take_array_ex": (ST, [VP, VP, INT, VP, U64, U32, VP, C.POINTER(VxgTakeInfo), VP]),
     "vxg_filter_array": (ST, [VP, VP, VP, VP, VP]),
     "vxg_compare_scalar": (ST, [VP, VP, INT, VP, U32, VP, C.POINTER(VxgCompareInfo), VP]),
     "vxg_compare_bytes": (ST, [VP, VP, INT, VP, U64, U32, VP, C.POINTER(VxgCompareBytesInfo), VP]),

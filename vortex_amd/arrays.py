@@ -536,7 +536,7 @@ class Canonical:
     validity: Any = None     # torch.uint8 LSB bitmap or None (no nulls)
     data_buffers: Any = None  # [(offset, len)] of each data buffer inside `data`
     binary: bool = False      # VarBinView of DType::Binary (else Utf8)
-    info: Any = None          # compare(): the vxg_compare_info counters (what ran), else None
+    info: Any = None          # compare() / take(): the call's info counters (what ran), else None
 
     def to_arrow(self):
         """Canonical::into_arrow (canonical.rs:71-85; varbinview/mod.rs:518 varbinview_as_arrow):
@@ -631,10 +631,15 @@ def canonicalize(a: Array, ctx: Context, out_values=None, sync: bool = True) -> 
     return res
 
 
-def take(a: Array, indices, ctx: Context, sync: bool = True) -> Canonical:
+def take(a: Array, indices, ctx: Context, sync: bool = True, force_canonical: bool = False) -> Canonical:
     """compute::take (vortex-array/src/compute/take.rs:10-34) on the compressed tree
-    (vxg_take_array): BitPacked / FoR / ZigZag / ALP cascades decode only the taken values, Dict
-    takes its codes; `indices` is a device tensor or host array of integers."""
+    (vxg_take_array_ex): BitPacked / FoR / ZigZag / ALP cascades decode only the taken values, Dict
+    takes its codes; `indices` is a device tensor or host array of integers.  A bool array gives a
+    Bool canonical; a utf8/binary array a VarBinView over one new heap of the taken rows in index
+    order, as `filter` gives it -- Dict, VarBin, VarBinView and FSST rows are read where they lie
+    (only the taken FSST rows are decoded), and the call is synchronous (`sync` is ignored: the heap
+    size is read back).  `res.info` holds vxg_take_info's counters (what ran); force_canonical
+    (VXG_TAKE_CANONICALIZE) canonicalizes the whole array first: the same bytes, for diagnostics."""
     import torch
     keep: list = []
     node = flatten(a, keep)
@@ -656,20 +661,47 @@ def take(a: Array, indices, ctx: Context, sync: bool = True) -> Canonical:
         it = torch.from_numpy(ia.view(np.uint8).copy()).to(dev)
     n = int(it.numel() if isinstance(indices, torch.Tensor) else np.asarray(indices).size)
     out = _lib.VxgCanonical()
-    w = ptype_width(a.ptype)
-    vals = torch.empty(max(n * w, 16), dtype=torch.uint8, device=dev)
-    out.values = vals.data_ptr()
+    kind = _kind(a)
+    if kind == "primitive":
+        nvb = n * ptype_width(a.ptype)
+        buf = torch.empty(max(nvb, 16), dtype=torch.uint8, device=dev)
+        out.values = buf.data_ptr()
+    elif kind == "bool":
+        nvb = ((n + 31) // 32) * 4
+        buf = torch.empty(nvb + 4, dtype=torch.uint8, device=dev)
+        out.values = buf.data_ptr()
+    else:
+        buf = torch.empty(max(16 * n, 16), dtype=torch.uint8, device=dev)
+        out.views = buf.data_ptr()
     vt = torch.empty(((n + 31) // 32) * 4 + 4, dtype=torch.uint8, device=dev) if a.nullable else None
     if vt is not None:
         out.validity = vt.data_ptr()
-    _lib.check(ctx.lib.vxg_take_array(ctx.handle, C.byref(node), PTYPE[ip], C.c_void_p(it.data_ptr()), n,
-                                      C.byref(out), ctx.stream_ptr()))
-    res = Canonical("primitive", n, a.ptype, values=vals[: n * w])
+    table = (_lib.VxgDataBuffer * 1)()
+    out.data_buffers, out.data_buffers_cap = table, 1
+    info = _lib.VxgTakeInfo()
+    flags = _lib.TAKE_CANONICALIZE if force_canonical else 0
+    _lib.check(ctx.lib.vxg_take_array_ex(ctx.handle, C.byref(node), PTYPE[ip], C.c_void_p(it.data_ptr()), n, flags,
+                                         C.byref(out), C.byref(info), ctx.stream_ptr()))
+    res = Canonical(kind, n, a.ptype, binary=a.dtype == DTYPE["BINARY"],
+                    info={f: int(getattr(info, f)) for f, _ in info._fields_})
+    if kind == "varbinview":
+        res.views = buf[: 16 * n]
+        hb = int(out.data_bytes)
+        heap = torch.empty(hb + 16, dtype=torch.uint8, device=dev)
+        if out.data:  # the engine sized and allocated the new heap: move it into a torch buffer (D2D)
+            _lib.check(ctx.lib.vxg_memcpy_d2d(ctx.handle, C.c_void_p(heap.data_ptr()), C.c_void_p(out.data), hb,
+                                              ctx.stream_ptr()))
+            ctx.sync()
+            _lib.check(ctx.lib.vxg_free(ctx.handle, C.c_void_p(out.data)))
+        res.data = heap[:hb]
+        res.data_buffers = [(int(table[i].offset), int(table[i].len)) for i in range(int(out.n_data_buffers))]
+    else:
+        res.values = buf[:nvb]
     if out.validity:
         if vt is None or out.validity != vt.data_ptr():
             raise VortexError(7, "engine allocated validity for a non-nullable dtype")
         res.validity = vt[: (n + 7) // 8]
-    if sync:
+    if sync or kind == "varbinview":
         ctx.sync()
     return res
 

@@ -456,13 +456,31 @@ vxg_status vxg_runend_decode(vxg_ctx* ctx, unsigned value_width, const void* val
     return launch_runend(int(value_width), c, ctx->c.err_word, S(stream));
 }
 
-vxg_status vxg_take_array(vxg_ctx* ctx, const vxg_array* a, int indices_ptype, const void* indices,
-                          uint64_t n_indices, vxg_canonical* out, void* stream) {
+vxg_status vxg_take_array_ex(vxg_ctx* ctx, const vxg_array* a, int indices_ptype, const void* indices,
+                             uint64_t n_indices, uint32_t flags, vxg_canonical* out, vxg_take_info* info,
+                             void* stream) {
     VXG_TRY(use_device(ctx));
     if (!a || !out || (n_indices && !indices)) return set_error(VXG_ERR_INVALID_ARGUMENT, "null array/indices/out");
     if (!ptype_is_int(indices_ptype)) return set_error(VXG_ERR_INVALID_ARGUMENT, "take indices must be integers");
+    vxg_take_info ti{};
     Planner p(ctx, S(stream));
-    return p.take(*a, indices, ptype_width(indices_ptype), ptype_is_signed(indices_ptype), n_indices, *out);
+    void* const in[4] = {out->values, out->validity, out->views, out->data};
+    const vxg_status st =
+        p.take(*a, indices, ptype_width(indices_ptype), ptype_is_signed(indices_ptype), n_indices, flags, *out, ti);
+    if (info) *info = ti;
+    if (st != VXG_OK) {  // nothing engine-allocated is handed back with an error
+        void** const cur[4] = {&out->values, &out->validity, &out->views, &out->data};
+        for (int i = 0; i < 4; i++) {
+            if (*cur[i] && *cur[i] != in[i]) (void)hipFree(*cur[i]);
+            *cur[i] = in[i];
+        }
+    }
+    return st;
+}
+
+vxg_status vxg_take_array(vxg_ctx* ctx, const vxg_array* a, int indices_ptype, const void* indices,
+                          uint64_t n_indices, vxg_canonical* out, void* stream) {
+    return vxg_take_array_ex(ctx, a, indices_ptype, indices, n_indices, 0, out, nullptr, stream);
 }
 
 vxg_status vxg_compare_scalar(vxg_ctx* ctx, const vxg_array* a, int op, const void* scalar_host, uint32_t flags,

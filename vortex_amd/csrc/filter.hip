@@ -258,6 +258,11 @@ vxg_status launch_filter_count(const uint64_t* mask, uint64_t n, uint64_t* tile_
     return hip_check(hipGetLastError(), "scan_tiles_kernel");
 }
 
+vxg_status launch_scan_tiles(uint64_t* a, uint64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(kScanBlock), 0, s, a, n);
+    return hip_check(hipGetLastError(), "scan_tiles_kernel");
+}
+
 vxg_status launch_filter_values(const uint64_t* mask, uint64_t n, const uint64_t* tile_off, const void* in, int width,
                                 void* out, hipStream_t s) {
     const uint64_t tiles = filter_tiles(n);

@@ -14,6 +14,10 @@ inline uint64_t filter_tiles(uint64_t n) { return (n + kFilterTileRows - 1) / kF
 // len zero).  tile_off: filter_tiles(n) + 1 u64; tile_off[tiles] = true_count after the scan.
 vxg_status launch_filter_count(const uint64_t* mask, uint64_t n, uint64_t* tile_off, hipStream_t s);
 
+// Exclusive scan of a[0, n) in place, a[n] = the total (one workgroup): the scan every tile-count
+// launch above and below ends with, for a caller that counts its tiles itself (take_str.hip).
+vxg_status launch_scan_tiles(uint64_t* a, uint64_t n, hipStream_t s);
+
 // Compact `width`-byte values (1,2,4,8,16) of the selected rows into out (tile_off scanned).
 vxg_status launch_filter_values(const uint64_t* mask, uint64_t n, const uint64_t* tile_off, const void* in,
                                 int width, void* out, hipStream_t s);

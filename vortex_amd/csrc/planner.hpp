@@ -31,6 +31,7 @@
 #include "env.hpp"
 #include "k1g.hpp"
 #include "take.hpp"
+#include "take_str.hpp"
 #include "vxg_internal.hpp"
 
 struct vxg_ctx {
@@ -115,8 +116,10 @@ class Planner {
     }
 
     vxg_status canonical(const vxg_array& a, vxg_canonical& out);
-    // compute::take on the compressed tree (take.hip): values + validity.take(indices)
-    vxg_status take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out);
+    // compute::take on the compressed tree (take.hip, take_str.hip): the rows at the indices +
+    // validity.take(indices); flags: VXG_TAKE_*; info: what ran
+    vxg_status take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, uint32_t flags, vxg_canonical& out,
+                    vxg_take_info& info);
     // compute::filter (filter.hip): the rows whose predicate bit is set + validity.filter
     vxg_status filter(const vxg_array& a, const vxg_array& pred, vxg_canonical& out);
     // compute::compare with a scalar (compare.hip): a Bool canonical, bit i = op(value i, scalar)
@@ -199,7 +202,12 @@ class Planner {
     vxg_status decode_alprd(const vxg_array& a, void* dst);
     vxg_status decode_sparse_values(const vxg_array& a, void* dst);
 
+    vxg_take_info* tinfo_ = nullptr;  // take(): the counters of the call under way
     vxg_status take_values(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, void* dst);
+    vxg_status take_codes(const vxg_array& codes, const void* idx, int iw, bool isg, uint64_t n, void* dst);
+    vxg_status take_validity(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out);
+    vxg_status take_strings(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, bool force,
+                            vxg_canonical& out, vxg_take_info& info);
     vxg_status take_patches(const vxg_array& sp, TakePatches& p);
     // A BitPacked-rooted cascade the fused compare kernel serves, validated (compare).
     struct CmpFused {

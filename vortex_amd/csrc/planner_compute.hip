@@ -31,6 +31,7 @@ vxg_status Planner::take_patches(const vxg_array& sp, TakePatches& p) {
 vxg_status Planner::take_values(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, void* dst) {
     if (n == 0) return VXG_OK;
     auto via_canonical = [&]() -> vxg_status {  // canonicalize, then take the primitive
+        if (tinfo_) tinfo_->fallback_arrays++;
         const void* pv;
         VXG_TRY(view_primitive(a, &pv));
         return launch_take(width(a), pv, a.len, iw, isg, idx, n, dst, ctx_->c.err_word, s_);
@@ -76,9 +77,10 @@ vxg_status Planner::take_values(const vxg_array& a, const void* idx, int iw, boo
         const vxg_array* codes = child(a, 1);
         if (!values || !codes || values->dtype != VXG_DTYPE_PRIMITIVE || !ptype_is_int(codes->ptype))
             return via_canonical();
+        if (tinfo_) tinfo_->dict_arrays++;
         void* tc;
         VXG_TRY(temp(n * width(*codes), &tc));
-        VXG_TRY(take_values(*codes, idx, iw, isg, n, tc));
+        VXG_TRY(take_codes(*codes, idx, iw, isg, n, tc));
         const void* pv;
         VXG_TRY(view_primitive(*values, &pv));
         return launch_take(width(*values), pv, values->len, width(*codes), false, tc, n, dst, ctx_->c.err_word, s_);
@@ -114,19 +116,21 @@ vxg_status Planner::take_values(const vxg_array& a, const void* idx, int iw, boo
         if (!child(*bp, 0)) return set_error(VXG_ERR_INVALID_ARGUMENT, "BitPacked patches child missing");
         VXG_TRY(take_patches(*child(*bp, 0), t.inner));
     }
+    if (tinfo_) tinfo_->packed_launches++;
     return launch_take_packed(T, epi, t, s_);
 }
 
-vxg_status Planner::take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out) {
-    if (a.dtype != VXG_DTYPE_PRIMITIVE) return set_error(VXG_ERR_NOT_IMPLEMENTED, "take supports primitive arrays");
-    out.kind = VXG_ENC_PRIMITIVE;
-    out.len = n;
-    out.dtype = a.dtype;
-    out.ptype = a.ptype;
-    out.values_bytes = n * width(a);
-    if (!out.values)
-        VXG_TRY(hip_check(hipMalloc(&out.values, out.values_bytes ? out.values_bytes : 16), "take values alloc"));
-    VXG_TRY(take_values(a, idx, iw, isg, n, out.values));
+// The codes of a Dict at the indices: the Dict is what the counters name (dict_arrays), so codes
+// that go through their canonical values do not count as a fallback of their own.
+vxg_status Planner::take_codes(const vxg_array& codes, const void* idx, int iw, bool isg, uint64_t n, void* dst) {
+    const uint32_t fb = tinfo_ ? tinfo_->fallback_arrays : 0;
+    const vxg_status st = take_values(codes, idx, iw, isg, n, dst);
+    if (tinfo_) tinfo_->fallback_arrays = fb;
+    return st;
+}
+
+// validity.take(indices): the array's validity into a temporary, then the bit gather.
+vxg_status Planner::take_validity(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, vxg_canonical& out) {
     const vxg_array* node;
     int kind;
     VXG_TRY(validity_source(a, &node, &kind));
@@ -141,6 +145,303 @@ vxg_status Planner::take(const vxg_array& a, const void* idx, int iw, bool isg, 
     if (!out.validity) VXG_TRY(hip_check(hipMalloc(&out.validity, bytes ? bytes : 4), "take validity alloc"));
     return launch_gather_bits(out.validity, idx, iw, isg, n, static_cast<const uint8_t*>(src), a.len, ctx_->c.err_word,
                               s_);
+}
+
+vxg_status Planner::take(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, uint32_t flags,
+                         vxg_canonical& out, vxg_take_info& info) {
+    if (flags & ~uint32_t(VXG_TAKE_CANONICALIZE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown take flags");
+    const bool force = (flags & VXG_TAKE_CANONICALIZE) != 0;
+    tinfo_ = &info;
+    if (is_string(a)) return take_strings(a, idx, iw, isg, n, force, out, info);
+    out.len = n;
+    out.dtype = a.dtype;
+    out.ptype = a.ptype;
+    if (a.dtype == VXG_DTYPE_BOOL) {  // bool/compute/take.rs: the canonical bits, gathered
+        out.kind = VXG_ENC_BOOL;
+        out.values_bytes = ((n + 31) / 32) * 4;
+        const uint64_t src_bytes = ((a.len + 31) / 32) * 4;
+        void* bits;
+        VXG_TRY(temp(src_bytes, &bits));
+        VXG_TRY(launch_copy_bytes(bits, nullptr, src_bytes ? src_bytes : 4, s_));
+        VXG_TRY(bools_into(a, bits, 0));
+        info.fallback_arrays++;
+        if (!out.values)
+            VXG_TRY(hip_check(hipMalloc(&out.values, out.values_bytes ? out.values_bytes : 4), "take bool alloc"));
+        VXG_TRY(launch_gather_bits(out.values, idx, iw, isg, n, static_cast<const uint8_t*>(bits), a.len,
+                                   ctx_->c.err_word, s_));
+        return take_validity(a, idx, iw, isg, n, out);
+    }
+    if (a.dtype != VXG_DTYPE_PRIMITIVE)
+        return set_error(VXG_ERR_NOT_IMPLEMENTED, "take supports primitive, bool and utf8/binary dtypes");
+    out.kind = VXG_ENC_PRIMITIVE;
+    out.values_bytes = n * width(a);
+    if (!out.values)
+        VXG_TRY(hip_check(hipMalloc(&out.values, out.values_bytes ? out.values_bytes : 16), "take values alloc"));
+    if (force) {  // VXG_TAKE_CANONICALIZE: the canonical values, then the gather
+        if (n) {
+            info.fallback_arrays++;
+            const void* pv;
+            VXG_TRY(view_primitive(a, &pv));
+            VXG_TRY(launch_take(width(a), pv, a.len, iw, isg, idx, n, out.values, ctx_->c.err_word, s_));
+        }
+    } else {
+        VXG_TRY(take_values(a, idx, iw, isg, n, out.values));
+    }
+    return take_validity(a, idx, iw, isg, n, out);
+}
+
+// take of a utf8 / binary array (take_str.hip): one new heap of the taken rows in index order, views
+// over it.  Dict takes its codes and gathers the dictionary's views; VarBin, VarBinView and FSST rows
+// are read where they lie; everything else (Chunked, a Dict of Chunked values, `force`) canonicalizes
+// the whole array into temporaries first.  Synchronous: the heap size is read back.
+vxg_status Planner::take_strings(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, bool force,
+                                 vxg_canonical& out, vxg_take_info& info) {
+    uint32_t* err = ctx_->c.err_word;
+    const TakeIdx tix{idx, n, a.len, iw, int(isg)};
+    auto bytes_of = [&](const vxg_array& b, const void** p) -> vxg_status {
+        if (b.dtype != VXG_DTYPE_PRIMITIVE || width(b) != 1)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "string bytes must be a u8 array");
+        return view_primitive(b, p);
+    };
+    // canonical views of `s` in temporaries + the base of each of their data buffers
+    auto canonical_views = [&](const vxg_array& s, const uint8_t** views, std::vector<const uint8_t*>& bases) -> vxg_status {
+        vxg_canonical src{};
+        std::vector<vxg_data_buffer> lay;
+        uint64_t extent;
+        VXG_TRY(string_layout(s, lay, extent));
+        const vxg_array* vnode;
+        int vkind;
+        VXG_TRY(validity_source(s, &vnode, &vkind));
+        if (vkind != 0) VXG_TRY(temp(((s.len + 31) / 32) * 4, &src.validity));
+        VXG_TRY(temp(16 * s.len, &src.views));
+        VXG_TRY(temp(extent + 16, &src.data));
+        src.data_bytes = extent;
+        src.data_buffers = lay.data();
+        src.n_data_buffers = src.data_buffers_cap = uint32_t(lay.size());
+        VXG_TRY(string_canonical(s, src));
+        *views = static_cast<const uint8_t*>(src.views);
+        bases.resize(lay.size());
+        for (size_t b = 0; b < lay.size(); b++) bases[b] = static_cast<const uint8_t*>(src.data) + lay[b].offset;
+        return VXG_OK;
+    };
+
+    // ---- classify and validate before any output is allocated ----
+    enum class Kind { Fallback, Dict, View, VarBin, Fsst } kind = Kind::Fallback;
+    const vxg_array *dvalues = nullptr, *dcodes = nullptr;
+    const void* src_views = nullptr;   // View
+    std::vector<StrBuf> vbufs;         // View: its buffers
+    CCol vb_offs{};                    // VarBin
+    const void* vb_bytes = nullptr;
+    uint64_t vb_bytes_len = 0;
+    TakeFsst fs{};
+    if (!force) switch (a.encoding) {
+    case VXG_ENC_DICT: {
+        dvalues = child(a, 0);
+        dcodes = child(a, 1);
+        if (!dvalues || !dcodes) return set_error(VXG_ERR_INVALID_ARGUMENT, "DictArray needs values and codes");
+        if (!ptype_is_int(dcodes->ptype) || dcodes->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "Dict codes must be integers");
+        if (dcodes->len != a.len) return set_error(VXG_ERR_INVALID_ARGUMENT, "Dict codes length != array length");
+        // Density rule (profiles/take_strings_bench.json, dict_shipmode): taking the codes first wins
+        // up to len / 4 (1.03-2.35x), ties at len / 2 and loses from n = len (0.96x, both index orders:
+        // as many codes are taken as the array holds, and they pass through a temporary that the
+        // fused codes -> views decode of the canonical path never writes): n >= len canonicalizes.
+        if (is_string(*dvalues) && dvalues->encoding != VXG_ENC_CHUNKED && n < a.len) kind = Kind::Dict;
+        break;
+    }
+    case VXG_ENC_VARBINVIEW: {
+        const vxg_array* vw = child(a, 0);
+        const uint32_t nb = a.meta.varbinview.n_buffers;
+        if (!vw || a.n_children < 1 + nb)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinViewArray: missing views/data buffers");
+        VXG_TRY(bytes_of(*vw, &src_views));
+        if (vw->len < 16 * a.len) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views shorter than 16 * len");
+        if (reinterpret_cast<uintptr_t>(src_views) & 15)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views must be 16-byte aligned");
+        vbufs.resize(nb);
+        for (uint32_t b = 0; b < nb; b++) {
+            const void* pb;
+            VXG_TRY(bytes_of(a.children[1 + b], &pb));
+            vbufs[b] = StrBuf{static_cast<const uint8_t*>(pb), a.children[1 + b].len};
+        }
+        kind = Kind::View;
+        break;
+    }
+    case VXG_ENC_VARBIN: {
+        const vxg_array* offs = child(a, 0);
+        const vxg_array* bytes = child(a, 1);
+        if (!offs || !bytes) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinArray needs offsets and bytes");
+        if (!ptype_is_int(offs->ptype) || offs->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "VarBin offsets must be integers");
+        if (offs->len < a.len + 1) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets shorter than len + 1");
+        if (bytes->len > 0xFFFFFFFFull) break;  // a view's offset is a u32: the canonical's several buffers
+        VXG_TRY(bytes_of(*bytes, &vb_bytes));
+        vb_bytes_len = bytes->len;
+        IntCol oc;
+        VXG_TRY(int_column(*offs, oc));
+        if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets must be aligned to their width");
+        vb_offs = to_ccol(oc);
+        kind = Kind::VarBin;
+        break;
+    }
+    case VXG_ENC_FSST: {
+        const vxg_array* sym = child(a, 0);
+        const vxg_array* slen = child(a, 1);
+        const vxg_array* codes = child(a, 2);
+        const vxg_array* ulen = child(a, 3);
+        if (!sym || !slen || !codes || !ulen || codes->encoding != VXG_ENC_VARBIN || !child(*codes, 0) || !child(*codes, 1))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSSTArray needs symbols, lengths, VarBin codes, lengths");
+        if (sym->len > 255 || slen->len < sym->len || width(*sym) != 8 || width(*slen) != 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbol table must hold at most 255 u64 symbols and their u8 lengths");
+        if (codes->len != a.len || ulen->len < a.len || child(*codes, 0)->len < a.len + 1)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST codes / lengths do not cover the array");
+        if (!ptype_is_int(child(*codes, 0)->ptype) || !ptype_is_int(ulen->ptype))
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "FSST offsets and lengths must be integers");
+        const void *psym, *pslen, *pcb;
+        VXG_TRY(view_primitive(*sym, &psym));
+        VXG_TRY(view_primitive(*slen, &pslen));
+        VXG_TRY(bytes_of(*child(*codes, 1), &pcb));
+        if (reinterpret_cast<uintptr_t>(psym) & 7) return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbols must be 8-byte aligned");
+        IntCol oc, lc;
+        VXG_TRY(int_column(*child(*codes, 0), oc));
+        VXG_TRY(int_column(*ulen, lc));
+        if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width) ||
+            reinterpret_cast<uintptr_t>(lc.p) % uint64_t(lc.packed ? 16 : lc.width))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST offsets / lengths must be aligned to their width");
+        fs.symbols = static_cast<const uint64_t*>(psym);
+        fs.sym_lens = static_cast<const uint8_t*>(pslen);
+        fs.codes = static_cast<const uint8_t*>(pcb);
+        fs.codes_len = child(*codes, 1)->len;
+        fs.offs = to_ccol(oc);
+        fs.lens = to_ccol(lc);
+        fs.n_symbols = uint32_t(sym->len);
+        fs.t = tix;
+        kind = Kind::Fsst;
+        break;
+    }
+    default: break;
+    }
+    if (reinterpret_cast<uintptr_t>(out.views) & 15)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "take: views must be 16-byte aligned");
+    (kind == Kind::Dict ? info.dict_arrays : kind == Kind::Fallback ? info.fallback_arrays : info.direct_arrays)++;
+
+    out.kind = VXG_ENC_VARBINVIEW;
+    out.len = n;
+    out.dtype = a.dtype;
+    out.ptype = a.ptype;
+
+    // ---- validity.take(indices), before the rows: a null row keeps no bytes ----
+    void* tcodes = nullptr;  // Dict: the codes at the indices
+    const int cw = dcodes ? width(*dcodes) : 0;
+    if (kind == Kind::Dict) {
+        VXG_TRY(temp(n * cw, &tcodes));
+        VXG_TRY(take_codes(*dcodes, idx, iw, isg, n, tcodes));
+        // values.validity().take(codes) (validity_into's Dict rule) from the codes already taken:
+        // work by n and the dictionary's size, not by len
+        const vxg_array* vnode;
+        int vkind;
+        VXG_TRY(validity_source(*dvalues, &vnode, &vkind));
+        if (vkind == 0) {
+            out.validity = nullptr;
+        } else {
+            void* vbits = nullptr;
+            VXG_TRY(temp(((dvalues->len + 31) / 32) * 4, &vbits));
+            VXG_TRY(validity_into(*dvalues, &vbits));
+            const uint64_t bytes = ((n + 31) / 32) * 4;
+            if (!out.validity) VXG_TRY(hip_check(hipMalloc(&out.validity, bytes ? bytes : 4), "take validity alloc"));
+            VXG_TRY(launch_gather_bits(out.validity, tcodes, cw, false, n, static_cast<const uint8_t*>(vbits),
+                                       dvalues->len, err, s_));
+        }
+    } else {
+        VXG_TRY(take_validity(a, idx, iw, isg, n, out));
+    }
+    const uint8_t* valid = static_cast<const uint8_t*>(out.validity);
+    if (!out.views) VXG_TRY(hip_check(hipMalloc(&out.views, n ? 16 * n : 16), "take views alloc"));
+    uint8_t* views = static_cast<uint8_t*>(out.views);
+
+    // the heap's size is known: check it against the caller's buffer, or allocate
+    auto size_heap = [&](uint64_t heap) -> vxg_status {
+        if (heap > 0xFFFFFFFFull) return set_error(VXG_ERR_INVALID_ARGUMENT, "taken string heap exceeds u32 view offsets");
+        if (out.data && out.data_bytes < heap)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "caller-provided data holds " + std::to_string(out.data_bytes) +
+                                                           " bytes, the taken heap needs " + std::to_string(heap));
+        if (!out.data) VXG_TRY(hip_check(hipMalloc(&out.data, heap + 16), "take heap alloc"));
+        out.data_bytes = heap;
+        out.n_data_buffers = 1;
+        if (out.data_buffers && out.data_buffers_cap >= 1) out.data_buffers[0] = vxg_data_buffer{0, heap};
+        return VXG_OK;
+    };
+    auto read_total = [&](const uint64_t* p, uint64_t* v) -> vxg_status {
+        VXG_TRY(hip_check(hipMemcpyAsync(v, p, 8, hipMemcpyDeviceToHost, s_), "take heap readback"));
+        return hip_check(hipStreamSynchronize(s_), "take heap sync");
+    };
+
+    if (kind == Kind::Fsst) {  // sizes from uncompressed_lengths, then decode only the taken rows
+        fs.valid = valid;
+        const uint64_t tiles = take_str_tiles(n);
+        void* toff;
+        VXG_TRY(temp((tiles + 1) * 8, &toff));
+        VXG_TRY(launch_take_fsst_sizes(fs, static_cast<uint64_t*>(toff), err, s_));
+        uint64_t heap = 0;
+        VXG_TRY(read_total(static_cast<uint64_t*>(toff) + tiles, &heap));
+        VXG_TRY(size_heap(heap));
+        VXG_TRY(launch_take_fsst_decode(fs, static_cast<const uint64_t*>(toff), static_cast<uint8_t*>(out.data), views, err,
+                                        s_));
+        return hip_check(hipStreamSynchronize(s_), "take sync");
+    }
+
+    // ---- source views of the taken rows, then filter's heap rebuild over their buffers ----
+    // The small host tables (`vbufs`, `bases`) are uploaded stream-ordered; the heap-size readback's
+    // sync drains those copies, so they cost no sync of their own.
+    std::vector<const uint8_t*> bases;
+    auto rows = [&]() -> vxg_status {
+        const uint64_t ktiles = filter_tiles(n);
+        void* hoff;
+        VXG_TRY(temp((ktiles + 1) * 8, &hoff));
+        uint64_t heap = 0;
+        if (kind == Kind::VarBin) {  // records, sizes, then one pass over the taken rows' bytes
+            VXG_TRY(launch_take_varbin_rows(tix, vb_offs, vb_bytes_len, valid, views, err, s_));
+            VXG_TRY(launch_view_heap_sizes(views, n, nullptr, static_cast<uint64_t*>(hoff), s_));
+            VXG_TRY(read_total(static_cast<uint64_t*>(hoff) + ktiles, &heap));
+            VXG_TRY(size_heap(heap));
+            return launch_take_varbin_build(views, n, static_cast<const uint64_t*>(hoff), static_cast<const uint8_t*>(vb_bytes),
+                                            static_cast<uint8_t*>(out.data), s_);
+        }
+        if (kind == Kind::Dict) {
+            const uint8_t* vviews;
+            VXG_TRY(canonical_views(*dvalues, &vviews, bases));
+            VXG_TRY(launch_take_views(vviews, dvalues->len, tcodes, cw, false, n, tix, nullptr, 0, valid, views, err, s_));
+        } else if (kind == Kind::View) {
+            void* dbufs;
+            VXG_TRY(temp(vbufs.size() * sizeof(StrBuf), &dbufs));
+            if (!vbufs.empty())
+                VXG_TRY(hip_check(hipMemcpyAsync(dbufs, vbufs.data(), vbufs.size() * sizeof(StrBuf), hipMemcpyHostToDevice, s_),
+                                  "take buffer table upload"));
+            for (const StrBuf& b : vbufs) bases.push_back(b.p);
+            VXG_TRY(launch_take_views(static_cast<const uint8_t*>(src_views), a.len, idx, iw, isg, n, TakeIdx{},
+                                      static_cast<const StrBuf*>(dbufs), uint32_t(vbufs.size()), valid, views, err, s_));
+        } else {
+            const uint8_t* cviews;
+            VXG_TRY(canonical_views(a, &cviews, bases));
+            VXG_TRY(launch_take_views(cviews, a.len, idx, iw, isg, n, TakeIdx{}, nullptr, 0, valid, views, err, s_));
+        }
+        void* dbases;
+        VXG_TRY(temp(bases.size() * sizeof(void*) + 8, &dbases));
+        if (!bases.empty())
+            VXG_TRY(hip_check(hipMemcpyAsync(dbases, bases.data(), bases.size() * sizeof(void*), hipMemcpyHostToDevice, s_),
+                              "take buffer table upload"));
+        VXG_TRY(launch_view_heap_sizes(views, n, valid, static_cast<uint64_t*>(hoff), s_));
+        VXG_TRY(read_total(static_cast<uint64_t*>(hoff) + ktiles, &heap));
+        VXG_TRY(size_heap(heap));
+        return launch_view_heap_build(views, n, valid, static_cast<const uint64_t*>(hoff),
+                                      static_cast<const uint8_t* const*>(dbases), uint32_t(bases.size()),
+                                      static_cast<uint8_t*>(out.data), err, s_);
+    };
+    const vxg_status st = rows();
+    // complete on return -- and, on an error too, nothing still reads `vbufs` / `bases`
+    const vxg_status sync = hip_check(hipStreamSynchronize(s_), "take sync");
+    return st != VXG_OK ? st : sync;
 }
 
 // ---- compute::compare with a scalar (vortex-array/src/compute/compare.rs:81-124) ----------
