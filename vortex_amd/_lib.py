@@ -175,6 +175,21 @@ class VxgCompareBytesInfo(C.Structure):
                 ("direct_launches", C.c_uint32), ("direct_chunks", C.c_uint32), ("fallback_arrays", C.c_uint32)]
 
 
+class VxgPredicate(C.Structure):
+    """vxg_predicate: one conjunct of vxg_row_filter, column <op> scalar."""
+    _fields_ = [("column", C.POINTER(VxgArray)), ("op", C.c_int32), ("reserved", C.c_uint32),
+                ("scalar_host", C.c_void_p), ("scalar_len", C.c_uint64)]
+
+
+class VxgRowFilterInfo(C.Structure):
+    _fields_ = [("predicates", C.c_uint32), ("range_pairs", C.c_uint32), ("compare_passes", C.c_uint32),
+                ("range_launches", C.c_uint32), ("fused_launches", C.c_uint32), ("fallback_arrays", C.c_uint32),
+                ("combine_launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ROWF_FUSE_RANGES, ROWF_NO_FUSE_RANGES = 1, 2  # VXG_ROWF_*; 0 = the engine's choice
+
+
 class VxgTakeInfo(C.Structure):
     _fields_ = [("packed_launches", C.c_uint32), ("dict_arrays", C.c_uint32), ("direct_arrays", C.c_uint32),
                 ("fallback_arrays", C.c_uint32)]
@@ -246,6 +261,7 @@ GPU_SIGNATURES = {
     "vxg_filter_array": (ST, [VP, VP, VP, VP, VP]),
     "vxg_compare_scalar": (ST, [VP, VP, INT, VP, U32, VP, C.POINTER(VxgCompareInfo), VP]),
     "vxg_compare_bytes": (ST, [VP, VP, INT, VP, U64, U32, VP, C.POINTER(VxgCompareBytesInfo), VP]),
+    "vxg_row_filter": (ST, [VP, C.POINTER(VxgPredicate), U32, U32, VP, VP, C.POINTER(VxgRowFilterInfo), VP]),
     "vxg_fsst_scratch_bytes": (U64, [U64]),
     "vxg_fsst_decode": (ST, [VP, VP, VP, UINT, VP, INT, VP, INT, VP, U64, VP, VP, VP, VP, VP]),
     "vxg_fill": (ST, [VP, UINT, VP, U64, VP, VP]),

@@ -536,7 +536,8 @@ class Canonical:
     validity: Any = None     # torch.uint8 LSB bitmap or None (no nulls)
     data_buffers: Any = None  # [(offset, len)] of each data buffer inside `data`
     binary: bool = False      # VarBinView of DType::Binary (else Utf8)
-    info: Any = None          # compare() / take(): the call's info counters (what ran), else None
+    info: Any = None          # compare() / take() / row_filter(): the call's info counters (what ran), else None
+    true_count: Any = None    # row_filter(count=True, sync=True): the number of set bits
 
     def to_arrow(self):
         """Canonical::into_arrow (canonical.rs:71-85; varbinview/mod.rs:518 varbinview_as_arrow):
@@ -808,6 +809,69 @@ def compare(a: Array, op: str, scalar, ctx: Context, null_as_false: bool = False
         res.validity = vt[:nbytes]
     if sync:
         ctx.sync()
+    return res
+
+
+def row_filter(preds, ctx: Context, flags: int = 0, sync: bool = True, out_values=None, count=True) -> Canonical:
+    """RowFilter::evaluate (vortex-serde/src/layouts/read/filtering.rs:27-43) on the GPU
+    (vxg_row_filter): the row mask of a conjunction.  `preds` is a list of (Array, op, scalar) --
+    op as in `compare`, scalar a number for a primitive column, bytes or str for a utf8/binary one.
+    The result is a non-nullable Bool canonical whose bit i is set where every conjunct is true and
+    its column is valid in row i, so `predicate_from(res)` is a filter predicate as it stands.
+    Each distinct Array OBJECT is flattened once: conjuncts on the same object share one node, and a
+    lower and an upper bound on one node are evaluated as one two-sided compare (`flags`:
+    0 = the engine's choice, _lib.ROWF_FUSE_RANGES, _lib.ROWF_NO_FUSE_RANGES; the bytes never
+    differ).  `res.info` holds vxg_row_filter_info's counters.  count: True = the true count is taken
+    on the device and, with sync, read back into `res.true_count`; a device uint8 tensor = its first
+    8 bytes (8-byte aligned) receive the count; False = no count.  `out_values` (a device uint8
+    tensor of ((len + 63) // 64) * 8 bytes, 8-byte aligned) is written in place."""
+    import torch
+    preds = list(preds)
+    if not preds:
+        raise VortexError(3, "row_filter: no conjunct")
+    keep: list = []
+    nodes: dict = {}
+    arr = (_lib.VxgPredicate * len(preds))()
+    for i, (a, op, scalar) in enumerate(preds):
+        if op not in _lib.CMP_OP:
+            raise VortexError(3, f"row_filter: unknown operator {op!r}")
+        if id(a) not in nodes:
+            node = flatten(a, keep)
+            keep.append(node)
+            nodes[id(a)] = node
+        arr[i].column = C.pointer(nodes[id(a)])
+        arr[i].op = _lib.CMP_OP[op]
+        if a.dtype in (DTYPE["UTF8"], DTYPE["BINARY"]):
+            sc = scalar.encode("utf-8") if isinstance(scalar, str) else bytes(scalar)
+            arr[i].scalar_len = len(sc)
+        else:
+            sc = np.array([scalar]).astype(NP_OF_PTYPE[a.ptype]).tobytes() if a.dtype == DTYPE["PRIMITIVE"] else bytes(8)
+        sbuf = (C.c_uint8 * max(len(sc), 8)).from_buffer_copy(sc.ljust(8, b"\0"))
+        keep.append(sbuf)
+        arr[i].scalar_host = C.cast(sbuf, C.c_void_p)
+    n = preds[0][0].len
+    dev = torch.device("cuda", ctx.device)
+    nbytes = ((n + 63) // 64) * 8
+    vals = out_values if out_values is not None else torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    out = _lib.VxgCanonical()
+    out.values = vals.data_ptr()
+    cnt = None
+    if isinstance(count, torch.Tensor):
+        cnt = count
+    elif count:
+        cnt = torch.empty(1, dtype=torch.int64, device=dev).view(torch.uint8)
+    info = _lib.VxgRowFilterInfo()
+    _lib.check(ctx.lib.vxg_row_filter(ctx.handle, arr, len(preds), int(flags), C.byref(out),
+                                      C.c_void_p(cnt.data_ptr()) if cnt is not None else None, C.byref(info),
+                                      ctx.stream_ptr()))
+    if out.validity:
+        raise VortexError(7, "engine returned a validity for a row filter")
+    res = Canonical("bool", n, "u8", values=vals[:nbytes],
+                    info={f: int(getattr(info, f)) for f, _ in info._fields_ if f != "reserved"})
+    if sync:
+        ctx.sync()
+        if cnt is not None:
+            res.true_count = int(cnt[:8].cpu().numpy().view(np.uint64)[0])
     return res
 
 

@@ -523,6 +523,47 @@ vxg_status vxg_compare_bytes(vxg_ctx* ctx, const vxg_array* a, int op, const voi
     return st;
 }
 
+vxg_status vxg_row_filter(vxg_ctx* ctx, const vxg_predicate* preds, uint32_t n_preds, uint32_t flags, vxg_canonical* out,
+                          uint64_t* true_count_dev, vxg_row_filter_info* info, void* stream) {
+    VXG_TRY(use_device(ctx));
+    if (!preds || !out || n_preds == 0) return set_error(VXG_ERR_INVALID_ARGUMENT, "row filter: null preds/out or no conjunct");
+    const uint32_t both = VXG_ROWF_FUSE_RANGES | VXG_ROWF_NO_FUSE_RANGES;
+    if ((flags & ~both) || (flags & both) == both) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown row filter flags");
+    if (reinterpret_cast<uintptr_t>(true_count_dev) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "row filter true count must be 8-byte aligned");
+    for (uint32_t i = 0; i < n_preds; i++) {  // every conjunct, before anything is launched or allocated
+        const vxg_predicate& p = preds[i];
+        const std::string at = "row filter conjunct " + std::to_string(i);
+        if (!p.column) return set_error(VXG_ERR_INVALID_ARGUMENT, at + ": null column");
+        if (p.reserved) return set_error(VXG_ERR_INVALID_ARGUMENT, at + ": reserved must be 0");
+        if (p.op < VXG_CMP_EQ || p.op > VXG_CMP_LTE)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, at + ": unknown compare operator " + std::to_string(p.op));
+        if (p.column->len != preds[0].column->len)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "Boolean operations aren't supported on arrays of different lengths");
+        if (p.column->dtype == VXG_DTYPE_PRIMITIVE) {
+            if (ptype_width(p.column->ptype) == 0 || p.column->ptype == VXG_F16)
+                return set_error(VXG_ERR_NOT_IMPLEMENTED, at + ": compare does not support f16");
+            if (!p.scalar_host) return set_error(VXG_ERR_INVALID_ARGUMENT, at + ": null scalar");
+        } else if (is_string(*p.column)) {
+            if (p.scalar_len && !p.scalar_host) return set_error(VXG_ERR_INVALID_ARGUMENT, at + ": null scalar");
+        } else if (p.column->dtype == VXG_DTYPE_BOOL) {
+            return set_error(VXG_ERR_NOT_IMPLEMENTED, at + ": Bool columns are not supported");
+        } else {
+            return set_error(VXG_ERR_MISMATCHED_TYPES, at + ": expected a primitive, utf8 or binary column");
+        }
+    }
+    vxg_row_filter_info ri{};
+    Planner p(ctx, S(stream));
+    const vxg_canonical in = *out;
+    const vxg_status st = p.row_filter(preds, n_preds, flags, *out, true_count_dev, ri);
+    if (info) *info = ri;
+    if (st != VXG_OK) {  // nothing engine-allocated is handed back with an error
+        if (out->values && out->values != in.values) (void)hipFree(out->values);
+        *out = in;
+    }
+    return st;
+}
+
 // ---- encoders on the GPU (encode_gpu.hip, fl_pack_impl.hpp) ----------------------------
 vxg_status vxg_compute_int_stats(vxg_ctx* ctx, int ptype, const void* values, uint64_t n, vxg_int_stats* out,
                                  void* stream) {

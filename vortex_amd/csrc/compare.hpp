@@ -63,4 +63,30 @@ vxg_status launch_cmp_patch_raw(int ptype, const TakePatches& p, uint64_t len, v
 // bits[w] &= mask[w] over n_words 64-bit words (values AND validity).
 vxg_status launch_and_words(void* bits, const void* mask, uint64_t n_words, hipStream_t s);
 
+// ---- the row filter's kernels (compare_range.hip) ---------------------------------------------
+// A range on one column as one test: lo_op (GT or GTE) against lo_bits AND hi_op (LT or LTE)
+// against hi_bits, the scalars as the little-endian bits of the compared type.
+struct CmpRange {
+    uint64_t lo_bits, hi_bits;
+    int lo_op, hi_op;
+};
+// The two-sided twins of the four launches above: the same arguments, bitmap store rules and launch
+// shapes, bit for bit the AND of the two one-sided results.
+vxg_status launch_cmp_range_packed(int T, Epi epi, int ck, const CmpTable& tab, uint64_t groups, uint32_t lds_bytes,
+                                   void* out, const CmpRange& r, hipStream_t s);
+vxg_status launch_cmp_range_plain(int ptype, const void* in, uint64_t n, void* out, uint64_t out_bit, const CmpRange& r,
+                                  bool excl, hipStream_t s);
+vxg_status launch_cmp_range_patch(int T, Epi epi, int ck, const TakePatches& p, uint64_t len, void* out, uint64_t out_bit,
+                                  const EpiParams& ep, const CmpRange& r, hipStream_t s);
+vxg_status launch_cmp_range_patch_raw(int ptype, const TakePatches& p, uint64_t len, void* out, uint64_t out_bit,
+                                      const CmpRange& r, uint32_t* err, hipStream_t s);
+// out[w] = p[0][w] & ... & p[k-1][w] over n_words 64-bit words (out may alias an input); with
+// `count`, the set bits of out are ADDED to *count (a device uint64 the caller zeroed on `s`).
+constexpr int kAndInputs = 16;
+struct AndInputs {
+    const uint64_t* p[kAndInputs];
+    uint32_t k;
+};
+vxg_status launch_and_count(const AndInputs& in, void* out, uint64_t n_words, uint64_t* count, hipStream_t s);
+
 }  // namespace vxg

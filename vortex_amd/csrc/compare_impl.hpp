@@ -1,7 +1,9 @@
 // compare_impl.hpp — the part of the packed-domain compare that does not depend on the predicate:
 // the bitmap store rule (put_word) and the walk over the FastLanes blocks of one chunk
-// (cmp_blocks).  compare.hip tests op(epilogue(value), scalar); compare_str.hip tests a bit of a
-// dictionary's truth table.  Device code only; included by those two units.
+// (cmp_blocks), with the small helpers of the numeric predicates (cmp_op, CmpV, scalar_of,
+// alp_factors, the patch position and bit assignment).  compare.hip tests op(epilogue(value),
+// scalar); compare_range.hip tests a lower and an upper bound at once; compare_str.hip tests a bit
+// of a dictionary's truth table.  Included by those three units only.
 #pragma once
 
 #include <type_traits>
@@ -13,6 +15,81 @@ namespace vxg {
 namespace {
 
 constexpr int kCmpThreads = 256;
+
+template <int OP, class V>
+__device__ __forceinline__ bool cmp_op(V v, V s) {
+    if constexpr (OP == VXG_CMP_EQ) return v == s;
+    else if constexpr (OP == VXG_CMP_NOT_EQ) return v != s;  // IEEE: true against NaN
+    else if constexpr (OP == VXG_CMP_GT) return v > s;
+    else if constexpr (OP == VXG_CMP_GTE) return v >= s;
+    else if constexpr (OP == VXG_CMP_LT) return v < s;
+    else return v <= s;
+}
+
+// The compared type of an epilogue output O: itself (unsigned, float) or its signed twin.
+template <class O, int CK>
+using CmpV = std::conditional_t<CK == kCmpSigned, std::make_signed_t<std::conditional_t<std::is_integral_v<O>, O, int>>, O>;
+
+template <class V>
+__device__ __forceinline__ V scalar_of(uint64_t bits) {
+    V s;
+    __builtin_memcpy(&s, &bits, sizeof(V));  // little-endian: the low bytes
+    return s;
+}
+
+// ALP's factors F10[f] and IF10[e] from the chunk's exponents: the reference's tables
+// (encodings/alp/src/alp/mod.rs:255-351; the same literals as capi.hip's, so the same bits).
+template <Epi EPI>
+__device__ __forceinline__ void alp_factors(uint32_t e, uint32_t f, double& a, double& b) {
+    if constexpr (EPI == Epi::AlpF32) {
+        constexpr float f10[11] = {1.0f, 10.0f, 100.0f, 1000.0f, 10000.0f, 100000.0f, 1000000.0f,
+                                   10000000.0f, 100000000.0f, 1000000000.0f, 10000000000.0f};
+        constexpr float if10[11] = {1.0f, 0.1f, 0.01f, 0.001f, 0.0001f, 0.00001f, 0.000001f,
+                                    0.0000001f, 0.00000001f, 0.000000001f, 0.0000000001f};
+        a = double(f10[f < 11 ? f : 0]);
+        b = double(if10[e < 11 ? e : 0]);
+    } else if constexpr (EPI == Epi::AlpF64) {
+        constexpr double f10[24] = {
+            1.0, 10.0, 100.0, 1000.0, 10000.0, 100000.0, 1000000.0, 10000000.0, 100000000.0,
+            1000000000.0, 10000000000.0, 100000000000.0, 1000000000000.0, 10000000000000.0,
+            100000000000000.0, 1000000000000000.0, 10000000000000000.0, 100000000000000000.0,
+            1000000000000000000.0, 10000000000000000000.0, 100000000000000000000.0,
+            1000000000000000000000.0, 10000000000000000000000.0, 100000000000000000000000.0};
+        constexpr double if10[24] = {
+            1.0, 0.1, 0.01, 0.001, 0.0001, 0.00001, 0.000001, 0.0000001, 0.00000001, 0.000000001,
+            0.0000000001, 0.00000000001, 0.000000000001, 0.0000000000001, 0.00000000000001,
+            0.000000000000001, 0.0000000000000001, 0.00000000000000001, 0.000000000000000001,
+            0.0000000000000000001, 0.00000000000000000001, 0.000000000000000000001,
+            0.0000000000000000000001, 0.00000000000000000000001};
+        a = f10[f < 24 ? f : 0];
+        b = if10[e < 24 ? e : 0];
+    } else {
+        a = b = 0.0;
+    }
+}
+
+// Patch position i of a Sparse patches child, relative to the array (compare.hip's patch kernels).
+__device__ __forceinline__ uint64_t patch_pos(const TakePatches& p, uint64_t i) {
+    uint64_t v;
+    switch (p.iw) {
+    case 1: v = p.isg ? uint64_t(int64_t(gload(static_cast<const int8_t*>(p.idx) + i))) : gload(static_cast<const uint8_t*>(p.idx) + i); break;
+    case 2: v = p.isg ? uint64_t(int64_t(gload(static_cast<const int16_t*>(p.idx) + i))) : gload(static_cast<const uint16_t*>(p.idx) + i); break;
+    case 4: v = p.isg ? uint64_t(int64_t(gload(static_cast<const int32_t*>(p.idx) + i))) : gload(static_cast<const uint32_t*>(p.idx) + i); break;
+    default: v = gload(static_cast<const uint64_t*>(p.idx) + i); break;
+    }
+    return v - p.off;
+}
+
+__device__ __forceinline__ void assign_bit(uint32_t* __restrict__ out, uint64_t bit, bool v) {
+    const uint32_t m = 1u << (bit & 31);
+    if (v) __hip_atomic_fetch_or(out + (bit >> 5), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else __hip_atomic_fetch_and(out + (bit >> 5), ~m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+unsigned cmp_grid(uint64_t n_threads) {
+    const uint64_t g = (n_threads + kCmpThreads - 1) / kCmpThreads;
+    return unsigned(g > 32768 ? 32768 : (g ? g : 1));
+}
 
 // One bitmap word of a producer that covers bits [cb, ce): `own` = all 64 bits of the word are
 // this producer's to write.

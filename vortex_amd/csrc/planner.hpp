@@ -128,6 +128,11 @@ class Planner {
     // compute::compare of a utf8/binary array with a scalar (compare_str.hip)
     vxg_status compare_bytes(const vxg_array& a, int op, const void* scalar_host, uint64_t scalar_len, uint32_t flags,
                              vxg_canonical& out, vxg_compare_bytes_info& info);
+    // RowFilter::evaluate (filtering.rs:27-43): the AND of the conjuncts' null_as_false compares and,
+    // with count_dev, its true count; a range on one column node is one two-sided compare
+    // (compare_range.hip).  The arguments are the entry point's, checked there.
+    vxg_status row_filter(const vxg_predicate* preds, uint32_t n_preds, uint32_t flags, vxg_canonical& out,
+                          uint64_t* count_dev, vxg_row_filter_info& info);
     vxg_status canonical_size(const vxg_array& a, uint64_t& vb, uint64_t& db);
     // Data buffers of a string canonical, placed 16-byte aligned in one allocation.
     vxg_status string_layout(const vxg_array& a, std::vector<vxg_data_buffer>& bufs, uint64_t& extent);
@@ -221,7 +226,11 @@ class Planner {
         bool excl;
     };
     vxg_status compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused);
-    vxg_status launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op);
+    vxg_status launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op,
+                                    const CmpRange* range);
+    // compare(); with `range`, both tests of a range in the same walk and launches
+    vxg_status compare_impl(const vxg_array& a, int op, uint64_t scalar_bits, const CmpRange* range, uint32_t flags,
+                            vxg_canonical& out, vxg_compare_info& info);
     // The string pieces of one row-compare target (the output bitmap, or the truth tables of the
     // Dict pieces), by kernel.
     struct StrRows {

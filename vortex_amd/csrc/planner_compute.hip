@@ -535,7 +535,8 @@ vxg_status Planner::compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused
 
 // The chunks of one kernel instantiation (T, epilogue, compared type; at most kCmpArgChunks) in one
 // launch: the table is the kernel argument -- nothing is uploaded and no host state outlives the call.
-vxg_status Planner::launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op) {
+vxg_status Planner::launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op,
+                                         const CmpRange* range) {
     uint64_t blocks = 0;
     for (const CmpFused* f : group) blocks += f->d.n_blocks();
     // small launches take fewer blocks per workgroup (>= 4: one per wave), like K1w's rule
@@ -556,14 +557,23 @@ vxg_status Planner::launch_compare_group(std::vector<CmpFused*>& group, void* ou
     if (groups == 0) groups = 1;  // an empty array: one workgroup that finds no block
     const CmpFused& f0 = *group[0];
     // (+ one word row of slack: a value's second word is read unconditionally)
+    if (range) return launch_cmp_range_packed(f0.T, f0.epi, f0.ck, tab, groups, lds + 128, out, *range, s_);
     return launch_cmp_packed(f0.T, f0.epi, f0.ck, tab, groups, lds + 128, out, scalar_bits, op, s_);
 }
 
 vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
                             vxg_compare_info& info) {
+    return compare_impl(a, op, scalar_bits, nullptr, flags, out, info);
+}
+
+// compare(), or with `range` the two tests of a range on one column in the same walk (row_filter):
+// every launch is then the two-sided twin of the one a single compare issues (op and scalar_bits
+// are not looked at).
+vxg_status Planner::compare_impl(const vxg_array& a, int op, uint64_t scalar_bits, const CmpRange* range, uint32_t flags,
+                                 vxg_canonical& out, vxg_compare_info& info) {
     if (a.dtype != VXG_DTYPE_PRIMITIVE) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare supports primitive arrays");
     if (width(a) == 0 || a.ptype == VXG_F16) return set_error(VXG_ERR_NOT_IMPLEMENTED, "compare does not support f16");
-    if (op < VXG_CMP_EQ || op > VXG_CMP_LTE)
+    if (!range && (op < VXG_CMP_EQ || op > VXG_CMP_LTE))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare operator " + std::to_string(op));
     if (flags & ~uint32_t(VXG_CMP_NULL_AS_FALSE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown compare flags");
     const uint64_t n = a.len, words = (n + 63) / 64, bytes = words * 8;
@@ -631,7 +641,7 @@ vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, ui
                order[j]->epi == order[i]->epi && order[j]->ck == order[i]->ck)
             j++;
         std::vector<CmpFused*> group(order.begin() + i, order.begin() + j);
-        VXG_TRY(launch_compare_group(group, out.values, scalar_bits, op));
+        VXG_TRY(launch_compare_group(group, out.values, scalar_bits, op, range));
         info.fused_launches++;
         info.fused_chunks += uint32_t(j - i);
         i = j;
@@ -641,14 +651,18 @@ vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, ui
         if (f.bp->meta.bitpacked.has_patches) {
             TakePatches tp;
             VXG_TRY(take_patches(*child(*f.bp, 0), tp));
-            VXG_TRY(launch_cmp_patch(f.T, f.epi, f.ck, tp, f.d.len(), out.values, f.d.out_bit, f.ep, scalar_bits, op, s_));
+            if (range) VXG_TRY(launch_cmp_range_patch(f.T, f.epi, f.ck, tp, f.d.len(), out.values, f.d.out_bit, f.ep, *range, s_));
+            else VXG_TRY(launch_cmp_patch(f.T, f.epi, f.ck, tp, f.d.len(), out.values, f.d.out_bit, f.ep, scalar_bits, op, s_));
             info.patch_launches += tp.n != 0;
         }
         if (f.outer) {
             TakePatches tp;
             VXG_TRY(take_patches(*f.outer, tp));
-            VXG_TRY(launch_cmp_patch_raw(a.ptype, tp, f.d.len(), out.values, f.d.out_bit, scalar_bits, op, ctx_->c.err_word,
-                                         s_));
+            if (range)
+                VXG_TRY(launch_cmp_range_patch_raw(a.ptype, tp, f.d.len(), out.values, f.d.out_bit, *range, ctx_->c.err_word, s_));
+            else
+                VXG_TRY(launch_cmp_patch_raw(a.ptype, tp, f.d.len(), out.values, f.d.out_bit, scalar_bits, op, ctx_->c.err_word,
+                                             s_));
             info.patch_launches += tp.n != 0;
         }
     }
@@ -658,7 +672,8 @@ vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, ui
         VXG_TRY(view_primitive(*p, &pv));
         if (reinterpret_cast<uintptr_t>(pv) % uint64_t(width(a)))
             return set_error(VXG_ERR_INVALID_ARGUMENT, "primitive buffer must be aligned to the value width");
-        VXG_TRY(launch_cmp_plain(a.ptype, pv, p->len, out.values, ob, scalar_bits, op, word_edges(ob, p->len), s_));
+        if (range) VXG_TRY(launch_cmp_range_plain(a.ptype, pv, p->len, out.values, ob, *range, word_edges(ob, p->len), s_));
+        else VXG_TRY(launch_cmp_plain(a.ptype, pv, p->len, out.values, ob, scalar_bits, op, word_edges(ob, p->len), s_));
         info.fallback_arrays++;
     }
 
@@ -686,6 +701,104 @@ vxg_status Planner::compare(const vxg_array& a, int op, uint64_t scalar_bits, ui
         VXG_TRY(launch_and_words(out.values, vbits, words, s_));
     }
     out.validity = null_as_false ? nullptr : vbits;
+    return VXG_OK;
+}
+
+// ---- RowFilter::evaluate (vortex-serde/src/layouts/read/filtering.rs:27-43) ----------------
+// One pass per conjunct -- or per range pair -- each into its own bitmap with null_as_false, then
+// the AND of the bitmaps (K21, compare_range.hip), which also takes the true count.  Nothing is
+// read back: the reference's early return at a zero count gives the same bits.
+vxg_status Planner::row_filter(const vxg_predicate* preds, uint32_t n_preds, uint32_t flags, vxg_canonical& out,
+                               uint64_t* count_dev, vxg_row_filter_info& info) {
+    const uint64_t n = preds[0].column->len, words = (n + 63) / 64, bytes = words * 8;
+    info.predicates = n_preds;
+
+    // pairing: per primitive column node, the i-th lower bound with the i-th upper bound in list order
+    struct Pass { uint32_t a, b; };  // conjunct a alone (b == a), or the range (lower a, upper b)
+    constexpr uint32_t kNone = ~0u;
+    std::vector<uint32_t> mate(n_preds, kNone);
+    if (!(flags & VXG_ROWF_NO_FUSE_RANGES)) {  // (flags 0: the default is to pair)
+        auto lower = [&](uint32_t i) { return preds[i].op == VXG_CMP_GT || preds[i].op == VXG_CMP_GTE; };
+        auto upper = [&](uint32_t i) { return preds[i].op == VXG_CMP_LT || preds[i].op == VXG_CMP_LTE; };
+        for (uint32_t i = 0; i < n_preds; i++) {
+            if (mate[i] != kNone || preds[i].column->dtype != VXG_DTYPE_PRIMITIVE || !(lower(i) || upper(i))) continue;
+            for (uint32_t j = i + 1; j < n_preds; j++) {  // the first unpaired bound of the other side
+                if (mate[j] != kNone || preds[j].column != preds[i].column) continue;
+                if (lower(i) ? !upper(j) : !lower(j)) continue;
+                // i is the first unpaired bound of its side: an earlier one would have taken j
+                mate[i] = j;
+                mate[j] = i;
+                break;
+            }
+        }
+    }
+    std::vector<Pass> passes;
+    for (uint32_t i = 0; i < n_preds; i++) {
+        if (mate[i] == kNone) passes.push_back({i, i});
+        else if (mate[i] > i) {
+            const bool lo_first = preds[i].op == VXG_CMP_GT || preds[i].op == VXG_CMP_GTE;
+            passes.push_back(lo_first ? Pass{i, mate[i]} : Pass{mate[i], i});
+        }
+    }
+    info.range_pairs = n_preds - uint32_t(passes.size());
+    info.compare_passes = uint32_t(passes.size());
+
+    out.kind = VXG_ENC_BOOL;
+    out.len = n;
+    out.dtype = VXG_DTYPE_BOOL;
+    out.ptype = VXG_U8;
+    out.values_bytes = bytes;
+    out.validity = nullptr;
+    if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, bytes ? bytes : 8), "row filter values alloc"));
+    if (reinterpret_cast<uintptr_t>(out.values) & 7)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "row filter output must be 8-byte aligned");
+
+    auto scalar_bits = [](const vxg_predicate& p) {
+        uint64_t bits = 0;
+        std::memcpy(&bits, p.scalar_host, size_t(ptype_width(p.column->ptype)));
+        return bits;
+    };
+    // the passes' bitmaps: one temporary for all of them, each on a 16-byte boundary
+    const uint64_t slot = (bytes + 15) & ~15ull;
+    void* slab = nullptr;
+    if (passes.size() > 1) VXG_TRY(temp(slot * passes.size(), &slab));
+    std::vector<void*> bitmaps;
+    for (const Pass& ps : passes) {
+        const vxg_predicate& p = preds[ps.a];
+        vxg_canonical c{};
+        // (a single pass: its bitmap is the output)
+        c.values = slab ? static_cast<uint8_t*>(slab) + slot * bitmaps.size() : out.values;
+        bitmaps.push_back(c.values);
+        if (is_string(*p.column)) {
+            vxg_compare_bytes_info bi{};
+            VXG_TRY(compare_bytes(*p.column, p.op, p.scalar_host, p.scalar_len, VXG_CMP_NULL_AS_FALSE, c, bi));
+            info.fused_launches += bi.dict_launches;
+            info.fallback_arrays += bi.fallback_arrays;
+            continue;
+        }
+        vxg_compare_info ci{};
+        if (ps.b != ps.a) {
+            const CmpRange r{scalar_bits(p), scalar_bits(preds[ps.b]), p.op, preds[ps.b].op};
+            VXG_TRY(compare_impl(*p.column, 0, 0, &r, VXG_CMP_NULL_AS_FALSE, c, ci));
+            info.range_launches += ci.fused_launches;
+        } else {
+            VXG_TRY(compare_impl(*p.column, p.op, scalar_bits(p), nullptr, VXG_CMP_NULL_AS_FALSE, c, ci));
+        }
+        info.fused_launches += ci.fused_launches;
+        info.fallback_arrays += ci.fallback_arrays;
+    }
+    if (bitmaps.size() == 1 && !count_dev) return VXG_OK;
+
+    if (count_dev) VXG_TRY(launch_copy_bytes(count_dev, nullptr, 8, s_));
+    // up to 16 bitmaps per launch, the running output among them from the second launch on; only
+    // the last launch counts (an earlier one would count rows a later bitmap still clears)
+    for (size_t i = 0; i < bitmaps.size();) {
+        AndInputs in{};
+        if (i) in.p[in.k++] = static_cast<const uint64_t*>(out.values);
+        while (in.k < uint32_t(kAndInputs) && i < bitmaps.size()) in.p[in.k++] = static_cast<const uint64_t*>(bitmaps[i++]);
+        VXG_TRY(launch_and_count(in, out.values, words, i == bitmaps.size() ? count_dev : nullptr, s_));
+        info.combine_launches += words != 0;
+    }
     return VXG_OK;
 }
 
