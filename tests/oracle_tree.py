@@ -349,8 +349,7 @@ def slice_primitive(a: Array, start: int, stop: int) -> Array:
     """primitive/compute/slice.rs:8-16 (buffer sub-range; validity sliced likewise)."""
     from vortex_amd import arrays as A
     vals = np.ascontiguousarray(a.buffers[0]).view(NP_OF_PTYPE[a.ptype])[start:stop]
-    mask = _validity(a)
-    return A.primitive(vals, a.ptype, validity=None if mask is None else mask[start:stop])
+    return A.primitive(vals, a.ptype, validity=_slice_validity(a, start, stop))
 
 
 def slice_sparse(sp: Array, start: int, stop: int) -> Array:
@@ -373,8 +372,6 @@ def slice_bitpacked(a: Array, start: int, stop: int) -> Array:
     physical positions (offset included), the new offset = physical start % 1024, patches sliced
     and dropped when the slice holds none."""
     from vortex_amd import arrays as A
-    if a.validity == VALIDITY["ARRAY"]:
-        raise NotImplementedError("slice of a BitPacked validity child")
     W, off0 = a.meta["bit_width"], a.meta["offset"]
     s, e = start + off0, stop + off0
     offset = s % 1024
@@ -385,18 +382,21 @@ def slice_bitpacked(a: Array, start: int, stop: int) -> Array:
         sp = slice_sparse(a.children[0], start, stop)
         if sp.children[0].len:
             patches = sp
-    return A.bitpacked(packed, a.ptype, W, stop - start, offset, patches,
-                       validity=None if a.validity == VALIDITY["NON_NULLABLE"] else "ALL_VALID")
+    return A.bitpacked(packed, a.ptype, W, stop - start, offset, patches, validity=_slice_validity(a, start, stop))
 
 
 def _slice_validity(a: Array, start: int, stop: int):
-    """Validity::slice (validity.rs): the metadata kinds stay, an Array child is sliced."""
+    """Validity::slice (validity.rs): the metadata kinds stay, an Array child is sliced -- a
+    BoolArray child by slice_bool (its bit offset moves), any other Bool encoding as its bits."""
     if a.validity == VALIDITY["NON_NULLABLE"]:
         return None
     if a.validity == VALIDITY["ALL_VALID"]:
         return "ALL_VALID"
     if a.validity == VALIDITY["ALL_INVALID"]:
         return "ALL_INVALID"
+    child = a.children[-1]
+    if child.dtype == DTYPE["BOOL"] and child.encoding == ENC["BOOL"] and child.validity == VALIDITY["NON_NULLABLE"]:
+        return slice_bool(child, start, stop)
     return _validity(a)[start:stop]
 
 
@@ -453,8 +453,75 @@ def slice_varbinview(a: Array, start: int, stop: int) -> Array:
     return A.varbinview(views, bufs, utf8=a.dtype == DTYPE["UTF8"], validity=_slice_validity(a, start, stop))
 
 
+def slice_for(a: Array, start: int, stop: int) -> Array:
+    """fastlanes/src/for/compute.rs:87-96: the encoded child sliced, reference and shift kept."""
+    from vortex_amd import arrays as A
+    ref = int(np.array([a.meta["reference"]], dtype=NP_OF_PTYPE[unsigned_of(a.ptype)]).view(NP_OF_PTYPE[a.ptype])[0])
+    return A.frame_of_reference(slice_any(a.children[0], start, stop), ref, a.meta["shift"], a.ptype)
+
+
+def slice_zigzag(a: Array, start: int, stop: int) -> Array:
+    """zigzag/src/compute.rs:68-72: the encoded child sliced."""
+    from vortex_amd import arrays as A
+    return A.zigzag(slice_any(a.children[0], start, stop))
+
+
+def slice_alp(a: Array, start: int, stop: int) -> Array:
+    """alp/src/alp/compute.rs:73-82: the encoded child sliced, the exponents kept, the patches
+    sliced as a SparseArray (kept even when the slice holds none of them)."""
+    from vortex_amd import arrays as A
+    patches = slice_any(a.children[1], start, stop) if a.meta["has_patches"] else None
+    return A.alp(slice_any(a.children[0], start, stop), a.meta["e"], a.meta["f"], patches)
+
+
+def slice_dict(a: Array, start: int, stop: int) -> Array:
+    """dict/src/compute.rs:60-65: the codes sliced, the values kept whole."""
+    from vortex_amd import arrays as A
+    return A.dict_array(a.children[0], slice_any(a.children[1], start, stop))
+
+
+def find_chunk_idx(a: Array, index: int) -> tuple[int, int]:
+    """ChunkedArray::find_chunk_idx (array/chunked/mod.rs:106-121): search_sorted(chunk_offsets,
+    index, Right).to_ends_index(nchunks + 1) - 1 (saturating): of several chunks that start at
+    `index` (empty ones before it) the last."""
+    offs = np.ascontiguousarray(a.children[0].buffers[0]).view(np.uint64)
+    i = int(np.searchsorted(offs, np.uint64(index), side="right"))
+    i = max((i - 1 if i == offs.size else i) - 1, 0)
+    return i, index - int(offs[i])
+
+
+def slice_chunked(a: Array, start: int, stop: int) -> Array:
+    """array/chunked/compute/slice.rs:7-36: the chunks holding start and stop and those between;
+    the first sliced from start to its end, the last up to stop -- or dropped when stop is its
+    first row; one chunk holding both is sliced once."""
+    from vortex_amd import arrays as A
+    c0, in0 = find_chunk_idx(a, start)
+    c1, in1 = find_chunk_idx(a, stop)
+    chunks = a.children[1:]
+    if c0 == c1:
+        return A.chunked([slice_any(chunks[c0], in0, in1)])
+    out = list(chunks[c0: c1 + 1])
+    out[0] = slice_any(out[0], in0, out[0].len)
+    if in1 == 0:
+        out.pop()
+    else:
+        out[-1] = slice_any(out[-1], 0, in1)
+    return A.chunked(out)
+
+
 def slice_any(a: Array, start: int, stop: int) -> Array:
-    """SliceFn restatements of the encodings the reference's slice KATs build."""
+    """SliceFn restatements: the encodings the reference's slice KATs build, and FoR, ZigZag, ALP,
+    Dict and Chunked for the seeded trees of tests/tree_cases.py -- metadata only, nothing decoded."""
+    if a.encoding == ENC["FL_FOR"]:
+        return slice_for(a, start, stop)
+    if a.encoding == ENC["ZIGZAG"]:
+        return slice_zigzag(a, start, stop)
+    if a.encoding == ENC["ALP"]:
+        return slice_alp(a, start, stop)
+    if a.encoding == ENC["DICT"]:
+        return slice_dict(a, start, stop)
+    if a.encoding == ENC["CHUNKED"]:
+        return slice_chunked(a, start, stop)
     if a.encoding == ENC["FL_BITPACKED"]:
         return slice_bitpacked(a, start, stop)
     if a.encoding == ENC["PRIMITIVE"]:

@@ -101,7 +101,7 @@ def test_c5_full_size_plan(ctx, lineitem_file_bytes):
     import time
     import torch
     import bench
-    from test_gpu_parity import plan_mode
+    from plan_env import plan_mode
     t0 = time.perf_counter()
     f = VortexFile(torch.from_numpy(lineitem_file_bytes).pin_memory())
     n = LI.n_chunks()

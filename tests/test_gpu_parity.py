@@ -5,7 +5,6 @@ MI355X with vxg_canonicalize (or a per-encoding entry point), and compares every
 with the oracle's CPU canonicalize of the same tree (tests/oracle_tree.py) — and with the
 original data (decode(encode(x)) == x).  Floating point is compared as raw bits.
 """
-import contextlib
 import ctypes as C
 import dataclasses
 
@@ -16,6 +15,7 @@ import vortex_amd as V
 import vortex_amd.arrays as A
 import vortex_amd.encode as E
 from oracle_tree import canon, view_bytes
+from plan_env import env_set, plan_mode
 
 pytestmark = pytest.mark.gpu
 
@@ -1215,30 +1215,6 @@ def sys_path_bench():
         sys.path.insert(0, root)
 
 
-class plan_mode:
-    """VXG_PLAN_BATCH for the plans created inside (plan.hip reads it at every vxg_plan_create):
-    "0" unbatched, "1" batched, "mixed", None = the default (plain create: the batched
-    candidate; measure=True: both recorded, vxg_plan_select keeps one)."""
-
-    def __init__(self, mode):
-        self.mode = mode
-
-    def __enter__(self):
-        import os
-        self.old = os.environ.get("VXG_PLAN_BATCH")
-        if self.mode is None:
-            os.environ.pop("VXG_PLAN_BATCH", None)
-        else:
-            os.environ["VXG_PLAN_BATCH"] = self.mode
-
-    def __exit__(self, *exc):
-        import os
-        if self.old is None:
-            os.environ.pop("VXG_PLAN_BATCH", None)
-        else:
-            os.environ["VXG_PLAN_BATCH"] = self.old
-
-
 def test_plan_graph_replay_matches_direct(ctx):
     """vxg_plan: the recorded HIP graph reproduces vxg_canonicalize's bytes on every replay,
     and a replay reads the CURRENT contents of the input buffers (new batch, same buffers)."""
@@ -1266,22 +1242,6 @@ def test_plan_graph_replay_matches_direct(ctx):
     dev[0].buffers[0].copy_(torch.from_numpy(np.ascontiguousarray(new.buffers[0]).view(np.uint8).reshape(-1).copy()))
     assert plan.launch(sync=True)[0].numpy().tobytes() == vals2.tobytes()
     plan.close()
-
-
-@contextlib.contextmanager
-def env_set(**kv):
-    """Environment variables set for the block (the planner reads these at plan recording)."""
-    import os
-    old = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.mark.parametrize("fuse,prepass", [("1", "ingrid"), ("1", "separate"), ("0", "separate")])
@@ -1716,6 +1676,43 @@ def test_plan_nested_chunked_not_deferred(ctx):
         assert res[-1].numpy()[0].tobytes() == rviews.tobytes()
         assert [b.tobytes() for b in res[-1].buffers()] == [b.tobytes() for b in rbufs]
     plan.close()
+
+
+def test_validity_of_a_cascade_over_a_nested_chunked(ctx):
+    """FoR / ZigZag / ALP take their validity from the encoded child.  When that child is a
+    ChunkedArray with nullable chunks the chunk validities are concatenated; the engine used to walk
+    the cascade node's own children instead (for ALP: its patches, read as the validity of a
+    null-fill Sparse).  Reduced from seed 56 of tests/tree_cases.py; direct, as a chunk, through a
+    plan and through take."""
+    rng = np.random.default_rng(5656)
+    n = 300
+    m = rng.random(n) < 0.6
+    u = rng.integers(0, 1 << 9, n).astype(np.uint32)
+    want_valid = m.copy()
+    want_valid[100:200] = True
+
+    def kids(v):
+        return A.chunked([A.primitive(v[:100], validity=m[:100]), A.primitive(v[100:200]),
+                          A.primitive(v[200:], validity=A.bool_array(m[200:], bit_offset=3))])
+
+    prices = np.round(rng.uniform(0, 100, n), 1).astype(np.float32)
+    prices[[3, 150, 299]] = (rng.standard_normal(3) * np.pi).astype(np.float32)
+    e, f, enc, idx, pv = E.alp_encode(prices)
+    assert idx.size >= 3
+    alp = A.alp(kids(enc), e, f, A.sparse(A.primitive(idx), A.primitive(pv, validity="ALL_VALID"), n))
+    arrs = [A.frame_of_reference(kids(u), 7, 0, "u32"), A.zigzag(kids(u)), alp,
+            A.chunked([A.primitive(prices[:10]), alp])]
+    for arr in arrs:
+        wv = want_valid if arr.len == n else np.concatenate([np.ones(10, bool), want_valid])
+        assert np.array_equal(canon(arr)[1], wv)
+        got = gpu(arr, ctx)
+        assert got.numpy().tobytes() == canon(arr)[0].tobytes()
+        assert np.array_equal(got.validity_mask(), wv), arr.encoding
+        plan = V.Plan([arr.to(torch_dev())], ctx)
+        assert np.array_equal(plan.launch(sync=True)[0].validity_mask(), wv), arr.encoding
+        plan.close()
+        ix = np.array([0, 99, 100, 199, 200, arr.len - 1, 5, 5], np.uint32)
+        assert np.array_equal(A.take(arr.to(torch_dev()), ix, ctx).validity_mask(), wv[ix]), arr.encoding
 
 
 def _alp_inner_outer(vals, outer, outer_vals):
@@ -2322,3 +2319,35 @@ def test_filter_errors(ctx):
     assert ei.value.kind == "InvalidArgument"
     with pytest.raises(V.VortexGpuError):
         A.filter(arr, A.primitive(np.ones(100, np.uint8)).to(torch_dev()), ctx)
+
+
+@pytest.mark.parametrize("n", [4096 * 1024, 4096 * 1024 + 1, 4096 * 1026 + 4097])
+def test_filter_many_tiles(ctx, n):
+    """The tile-offset scan (scan_tiles_kernel, one workgroup of 1024 threads, ceil(tiles / 1024)
+    entries each) at and past 1024 tiles of 4096 rows: 1024 tiles (one entry per thread, every
+    thread busy), 1025 (two entries per thread, the upper half of the threads clamped to empty
+    ranges) and 1028 with a ragged last tile; u8 values against numpy's vals[mask].  The largest
+    size once more with a nullable array, so that filter_bits_kernel crosses the same boundary."""
+    rng = np.random.default_rng(n)
+    vals = rng.integers(0, 256, n, dtype=np.uint8)
+    last_tile = np.zeros(n, bool)
+    t0 = ((n - 1) // 4096) * 4096
+    last_tile[t0:] = rng.random(n - t0) < 0.5
+    last_tile[n - 1] = True
+    ends = np.zeros(n, bool)
+    ends[[0, n - 1]] = True
+    masks = {"half": rng.random(n) < 0.5, "last tile only": last_tile, "first and last row": ends}
+    arrs = {"non-nullable": (A.primitive(vals), None)}
+    if n == 4096 * 1026 + 4097:
+        valid = rng.random(n) < 0.7
+        arrs["nullable"] = (A.primitive(vals, validity=valid), valid)
+    for aname, (arr, valid) in arrs.items():
+        dev = arr.to(torch_dev())
+        for mname, m in masks.items():
+            got = A.filter(dev, A.bool_array(m).to(torch_dev()), ctx)
+            assert got.len == int(m.sum()), (aname, mname)
+            assert got.numpy().tobytes() == vals[m].tobytes(), (aname, mname)
+            if valid is None:
+                assert got.validity is None, (aname, mname)
+            else:
+                assert np.array_equal(got.validity_mask(), valid[m]), (aname, mname)

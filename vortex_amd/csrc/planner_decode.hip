@@ -587,9 +587,12 @@ vxg_status Planner::validity_into(const vxg_array& a, void** bitmap) {
                                 node->meta.boolean.first_byte_bit_offset, a.len, false, s_);
     }
     if (kind == 5) return bools_into(*node, *bitmap, 0);
+    // kinds 6, 3 and 4 name the Dict / Sparse / Chunked node itself: `a`, or the node a FoR / ZigZag /
+    // ALP / ALP-RD / FSST array inherits its validity from (validity_source's recursion)
+    const vxg_array& src = *node;
     if (kind == 6) {  // Dict with nullable values: bit i = values_valid[codes[i]]
-        const vxg_array* vals = child(a, 0);
-        const vxg_array* codes = child(a, 1);
+        const vxg_array* vals = child(src, 0);
+        const vxg_array* codes = child(src, 1);
         if (!vals || !codes) return set_error(VXG_ERR_INVALID_ARGUMENT, "DictArray needs values and codes");
         if (!ptype_is_int(codes->ptype)) return set_error(VXG_ERR_MISMATCHED_TYPES, "Dict codes must be integers");
         void* vbits = nullptr;
@@ -601,16 +604,16 @@ vxg_status Planner::validity_into(const vxg_array& a, void** bitmap) {
                                   ctx_->c.err_word, s_);
     }
     if (kind == 3) {  // Sparse with null fill: valid exactly at the indices (flatten.rs:82-93)
-        const vxg_array* idx = child(a, 0);
+        const vxg_array* idx = child(src, 0);
         const void* pi;
         VXG_TRY(view_primitive(*idx, &pi));
         return launch_set_bits_at(*bitmap, pi, width(*idx), ptype_is_signed(idx->ptype),
-                                  a.meta.sparse.indices_offset, idx->len, a.len, s_);
+                                  src.meta.sparse.indices_offset, idx->len, a.len, s_);
     }
     // kind 4: chunked concatenation of chunk validities
     uint64_t off = 0;
-    for (uint32_t i = 1; i < a.n_children; i++) {
-        const vxg_array& c = a.children[i];
+    for (uint32_t i = 1; i < src.n_children; i++) {
+        const vxg_array& c = src.children[i];
         const vxg_array* n2;
         int k2;
         VXG_TRY(validity_source(c, &n2, &k2));
