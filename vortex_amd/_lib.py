@@ -190,6 +190,15 @@ class VxgRowFilterInfo(C.Structure):
 ROWF_FUSE_RANGES, ROWF_NO_FUSE_RANGES = 1, 2  # VXG_ROWF_*; 0 = the engine's choice
 
 
+class VxgFilterBatchInfo(C.Structure):
+    _fields_ = [("columns", C.c_uint32), ("mask_scans", C.c_uint32), ("syncs", C.c_uint32),
+                ("packed_launches", C.c_uint32), ("packed_chunks", C.c_uint32), ("patch_launches", C.c_uint32),
+                ("inplace_arrays", C.c_uint32), ("fallback_arrays", C.c_uint32)]
+
+
+FILTB_CANONICALIZE = 1  # VXG_FILTB_CANONICALIZE
+
+
 class VxgTakeInfo(C.Structure):
     _fields_ = [("packed_launches", C.c_uint32), ("dict_arrays", C.c_uint32), ("direct_arrays", C.c_uint32),
                 ("fallback_arrays", C.c_uint32)]
@@ -262,6 +271,8 @@ GPU_SIGNATURES = {
     "vxg_compare_scalar": (ST, [VP, VP, INT, VP, U32, VP, C.POINTER(VxgCompareInfo), VP]),
     "vxg_compare_bytes": (ST, [VP, VP, INT, VP, U64, U32, VP, C.POINTER(VxgCompareBytesInfo), VP]),
     "vxg_row_filter": (ST, [VP, C.POINTER(VxgPredicate), U32, U32, VP, VP, C.POINTER(VxgRowFilterInfo), VP]),
+    "vxg_filter_batch": (ST, [VP, C.POINTER(C.POINTER(VxgArray)), U32, VP, U64, U32, C.POINTER(VxgCanonical),
+                              C.POINTER(U64), C.POINTER(VxgFilterBatchInfo), VP]),
     "vxg_fsst_scratch_bytes": (U64, [U64]),
     "vxg_fsst_decode": (ST, [VP, VP, VP, UINT, VP, INT, VP, INT, VP, U64, VP, VP, VP, VP, VP]),
     "vxg_fill": (ST, [VP, UINT, VP, U64, VP, VP]),

@@ -875,6 +875,90 @@ def row_filter(preds, ctx: Context, flags: int = 0, sync: bool = True, out_value
     return res
 
 
+def filter_batch(columns, mask, ctx: Context, flags: int = 0, sync: bool = True, length=None):
+    """filter(batch, mask), the scan's step after `row_filter` (vortex-serde layouts/read/stream.rs:
+    143-149) on the GPU (vxg_filter_batch): every column of `columns` (Arrays of one length) filtered
+    by ONE device mask, which is counted and scanned once.  `mask` is a Bool Canonical without
+    validity -- a `row_filter` result, or a `compare(..., null_as_false=True)` one -- passed as it
+    stands, or a device uint8 tensor of ((length + 63) // 64) * 8 bytes (8-byte aligned) with
+    `length` rows; bits past the length are ignored.  BitPacked / FoR / ZigZag / ALP cascades (and
+    Chunked columns of those) are filtered in the packed domain, Primitive arrays from their own
+    buffers, everything else through its canonical values (`flags=_lib.FILTB_CANONICALIZE`: every
+    column; the bytes never differ).  Returns (list of Canonical, true_count, info): each Canonical is
+    what `filter(column, predicate)` gives; info holds vxg_filter_batch_info's counters.  With
+    sync=False primitive and bool outputs are complete at the next `ctx.sync()`."""
+    import torch
+    columns = list(columns)
+    if isinstance(mask, Canonical):
+        if mask.kind != "bool":
+            _bail("MismatchedTypes", "filter_batch needs a Bool canonical as its mask")
+        if mask.validity is not None:
+            _bail("InvalidArgument", "mask must be non-nullable bool: compare with null_as_false=True")
+        n, mt, k_hint = mask.len, mask.values, mask.true_count
+    else:
+        if length is None:
+            _bail("InvalidArgument", "filter_batch: a tensor mask needs its length")
+        n, mt, k_hint = int(length), mask, None
+    dev = torch.device("cuda", ctx.device)
+    keep: list = []
+    nodes = [flatten(a, keep) for a in columns]
+    cols = (C.POINTER(_lib.VxgArray) * max(len(columns), 1))(*[C.pointer(nd) for nd in nodes])
+    outs = (_lib.VxgCanonical * max(len(columns), 1))()
+    cap = n if k_hint is None else int(k_hint)  # rows every output has room for
+    bufs, vts, tables = [], [], []
+    for i, a in enumerate(columns):
+        kind = _kind(a)
+        if kind == "primitive":
+            buf = torch.empty(max(cap * ptype_width(a.ptype), 16), dtype=torch.uint8, device=dev)
+            outs[i].values = buf.data_ptr()
+        elif kind == "bool":
+            buf = torch.empty(((cap + 31) // 32) * 4 + 4, dtype=torch.uint8, device=dev)
+            outs[i].values = buf.data_ptr()
+        else:
+            buf = torch.empty(max(16 * cap, 16), dtype=torch.uint8, device=dev)
+            outs[i].views = buf.data_ptr()
+        vt = torch.empty(((cap + 31) // 32) * 4 + 4, dtype=torch.uint8, device=dev) if a.nullable else None
+        if vt is not None:
+            outs[i].validity = vt.data_ptr()
+        table = (_lib.VxgDataBuffer * 1)()
+        outs[i].data_buffers, outs[i].data_buffers_cap = table, 1
+        bufs.append(buf)
+        vts.append(vt)
+        tables.append(table)
+    k = C.c_uint64()
+    info = _lib.VxgFilterBatchInfo()
+    _lib.check(ctx.lib.vxg_filter_batch(ctx.handle, cols, len(columns), C.c_void_p(mt.data_ptr()) if n else None, n,
+                                        int(flags), outs, C.byref(k), C.byref(info), ctx.stream_ptr()))
+    kk = int(k.value)
+    res = []
+    for i, a in enumerate(columns):
+        kind, out, buf = _kind(a), outs[i], bufs[i]
+        r = Canonical(kind, kk, a.ptype, binary=a.dtype == DTYPE["BINARY"])
+        if kind == "primitive":
+            r.values = buf[: kk * ptype_width(a.ptype)]
+        elif kind == "bool":
+            r.values = buf[: ((kk + 31) // 32) * 4]
+        else:
+            r.views = buf[: 16 * kk]
+            hb = int(out.data_bytes)
+            heap = torch.empty(hb + 16, dtype=torch.uint8, device=dev)
+            if out.data:  # the engine sized and allocated the new heap: move it into a torch buffer (D2D)
+                _lib.check(ctx.lib.vxg_memcpy_d2d(ctx.handle, C.c_void_p(heap.data_ptr()), C.c_void_p(out.data), hb,
+                                                  ctx.stream_ptr()))
+                ctx.sync()
+                _lib.check(ctx.lib.vxg_free(ctx.handle, C.c_void_p(out.data)))
+            r.data = heap[:hb]
+            r.data_buffers = [(0, hb)]
+        if out.validity:
+            if vts[i] is None or out.validity != vts[i].data_ptr():
+                raise VortexError(7, "engine allocated validity for a non-nullable dtype")
+            r.validity = vts[i][: (kk + 7) // 8]
+        res.append(r)
+    if sync:
+        ctx.sync()
+    return res, kk, {f: int(getattr(info, f)) for f, _ in info._fields_}
+
+
 def predicate_from(mask: Canonical) -> Array:
     """A non-nullable Bool Array over the device bitmap of a Bool canonical (no host round trip):
     `filter(a, predicate_from(compare(a, "<", s, ctx, null_as_false=True)), ctx)`."""

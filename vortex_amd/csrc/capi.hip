@@ -676,6 +676,45 @@ vxg_status vxg_filter_array(vxg_ctx* ctx, const vxg_array* a, const vxg_array* p
     return hip_check(hipStreamSynchronize(S(stream)), "filter sync");
 }
 
+vxg_status vxg_filter_batch(vxg_ctx* ctx, const vxg_array* const* columns, uint32_t n_columns, const void* mask,
+                            uint64_t len, uint32_t flags, vxg_canonical* outs, uint64_t* true_count,
+                            vxg_filter_batch_info* info, void* stream) {
+    VXG_TRY(use_device(ctx));
+    if (n_columns == 0 || !columns || !outs)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "filter batch: null columns/outs or no column");
+    if (len && !mask) return set_error(VXG_ERR_INVALID_ARGUMENT, "filter batch: null mask");
+    if (reinterpret_cast<uintptr_t>(mask) & 7) return set_error(VXG_ERR_INVALID_ARGUMENT, "filter batch: mask must be 8-byte aligned");
+    if (flags & ~uint32_t(VXG_FILTB_CANONICALIZE)) return set_error(VXG_ERR_INVALID_ARGUMENT, "unknown filter batch flags");
+    for (uint32_t i = 0; i < n_columns; i++) {  // every column, before anything is launched or allocated
+        const vxg_array* a = columns[i];
+        if (!a) return set_error(VXG_ERR_INVALID_ARGUMENT, "filter batch column " + std::to_string(i) + ": null column");
+        if (a->len != len)  // filter.rs:33-39
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "predicate.len() is " + std::to_string(len) +
+                                                           ", does not equal array.len() of " + std::to_string(a->len));
+        if (!is_string(*a) && a->dtype != VXG_DTYPE_BOOL && a->dtype != VXG_DTYPE_PRIMITIVE)
+            return set_error(VXG_ERR_NOT_IMPLEMENTED, "filter supports primitive, bool and utf8/binary dtypes");
+    }
+    vxg_filter_batch_info fi{};
+    const std::vector<vxg_canonical> in(outs, outs + n_columns);
+    vxg_status st;
+    {
+        Planner p(ctx, S(stream));
+        st = p.filter_batch(columns, n_columns, mask, len, flags, outs, true_count, fi);
+    }
+    if (info) *info = fi;
+    if (st != VXG_OK) {  // nothing engine-allocated is handed back with an error
+        (void)hipStreamSynchronize(S(stream));  // (launches of earlier columns may still write them)
+        for (uint32_t i = 0; i < n_columns; i++) {
+            void* const cur[4] = {outs[i].values, outs[i].validity, outs[i].views, outs[i].data};
+            void* const was[4] = {in[i].values, in[i].validity, in[i].views, in[i].data};
+            for (int b = 0; b < 4; b++)
+                if (cur[b] && cur[b] != was[b]) (void)hipFree(cur[b]);
+            outs[i] = in[i];
+        }
+    }
+    return st;
+}
+
 vxg_status vxg_runend_bool_decode(vxg_ctx* ctx, int ends_ptype, const void* ends, uint64_t n_runs, uint64_t offset,
                                   int start, uint64_t len, void* out_bits, uint64_t out_bit_offset, void* stream) {
     VXG_TRY(use_device(ctx));

@@ -3,7 +3,8 @@
 // (cmp_blocks), with the small helpers of the numeric predicates (cmp_op, CmpV, scalar_of,
 // alp_factors, the patch position and bit assignment).  compare.hip tests op(epilogue(value),
 // scalar); compare_range.hip tests a lower and an upper bound at once; compare_str.hip tests a bit
-// of a dictionary's truth table.  Included by those three units only.
+// of a dictionary's truth table.  filter_packed.hip takes the small helpers (alp_factors, patch_pos,
+// cmp_table_index) for its own walk.  Included by those four units only.
 #pragma once
 
 #include <type_traits>

@@ -17,53 +17,22 @@
 // Strings additionally rebuild the heap: lengths from the compacted views, a tile scan of them,
 // then each thread copies its strings and rewrites their views (buffer 0, new offset) — the
 // layout arrow-cast gives the filtered VarBin (varbin/flatten.rs:10-17, Appendix C).
-#include "filter.hpp"
+#include "filter_impl.hpp"
 
 namespace vxg {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kFilterBlock = 256;  // 4 wavefronts = 4 tiles
 constexpr int kScanBlock = 1024;
 constexpr int kHeapRowsPerThread = 16;  // heap kernels: 256 threads x 16 rows = one 4096-row tile
-
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, int lane) {
-    const uint32_t lo = __builtin_amdgcn_readlane(uint32_t(v), lane);
-    const uint32_t hi = __builtin_amdgcn_readlane(uint32_t(v >> 32), lane);
-    return (uint64_t(hi) << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v, int lane) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d, kWave);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_or(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) v |= __shfl_xor(v, d, kWave);
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
-__device__ __forceinline__ uint64_t lanes_below(int lane) { return lane ? (~0ull >> (64 - lane)) : 0ull; }
 
 __global__ __launch_bounds__(kFilterBlock) void filter_count_kernel(const uint64_t* __restrict__ mask, uint64_t n,
                                                                     uint64_t* __restrict__ tile_off, uint64_t tiles) {
     const int lane = threadIdx.x % kWave;
     const uint64_t t = uint64_t(blockIdx.x) * (kFilterBlock / kWave) + threadIdx.x / kWave;
     if (t >= tiles) return;
-    const uint64_t nw = (n + 63) / 64, wi = t * 64 + lane;
-    const uint64_t c = wi < nw ? uint64_t(__popcll(mask[wi])) : 0;
+    const uint64_t c = uint64_t(__popcll(filter_mask_word(mask, n, t * 64 + lane)));
     const uint64_t sum = wave_sum(c);
     if (lane == 0) tile_off[t] = sum;
 }
@@ -101,21 +70,6 @@ template <> struct Cell<2> { using T = uint16_t; };
 template <> struct Cell<4> { using T = uint32_t; };
 template <> struct Cell<8> { using T = uint64_t; };
 template <> struct Cell<16> { using T = uint4; };
-
-// Per wavefront: the mask word of this lane and the output base of its first selected row.
-struct TileWords {
-    uint64_t m, base;
-};
-
-__device__ __forceinline__ TileWords tile_words(const uint64_t* __restrict__ mask, uint64_t n,
-                                                const uint64_t* __restrict__ tile_off, uint64_t t, int lane) {
-    const uint64_t nw = (n + 63) / 64, wi = t * 64 + lane;
-    TileWords r;
-    r.m = wi < nw ? mask[wi] : 0;
-    const uint64_t c = uint64_t(__popcll(r.m));
-    r.base = tile_off[t] + wave_incl_scan(c, lane) - c;
-    return r;
-}
 
 template <int W>
 __global__ __launch_bounds__(kFilterBlock) void filter_values_kernel(const uint64_t* __restrict__ mask, uint64_t n,

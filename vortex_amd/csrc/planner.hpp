@@ -122,6 +122,11 @@ class Planner {
                     vxg_take_info& info);
     // compute::filter (filter.hip): the rows whose predicate bit is set + validity.filter
     vxg_status filter(const vxg_array& a, const vxg_array& pred, vxg_canonical& out);
+    // filter(batch, mask) (filter_packed.hip): every column by one device mask, counted and scanned
+    // once; packed cascades are filtered where they lie.  The arguments are the entry point's,
+    // checked there.
+    vxg_status filter_batch(const vxg_array* const* cols, uint32_t n_cols, const void* mask, uint64_t n, uint32_t flags,
+                            vxg_canonical* outs, uint64_t* true_count, vxg_filter_batch_info& info);
     // compute::compare with a scalar (compare.hip): a Bool canonical, bit i = op(value i, scalar)
     vxg_status compare(const vxg_array& a, int op, uint64_t scalar_bits, uint32_t flags, vxg_canonical& out,
                        vxg_compare_info& info);
@@ -206,6 +211,10 @@ class Planner {
     vxg_status decode_chunked_primitive(const vxg_array& a, void* dst);
     vxg_status decode_alprd(const vxg_array& a, void* dst);
     vxg_status decode_sparse_values(const vxg_array& a, void* dst);
+
+    // filter() after the count: canonicalize `a` into temporaries, compact by the counted mask
+    vxg_status filter_selected(const vxg_array& a, const uint64_t* m, const uint64_t* to, uint64_t k, vxg_canonical& out,
+                               uint32_t* syncs);
 
     vxg_take_info* tinfo_ = nullptr;  // take(): the counters of the call under way
     vxg_status take_values(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, void* dst);

@@ -7,6 +7,7 @@
 #include <tuple>
 
 #include "filter.hpp"
+#include "filter_packed.hpp"
 #include "planner.hpp"
 
 namespace vxg {
@@ -1216,7 +1217,19 @@ vxg_status Planner::filter(const vxg_array& a, const vxg_array& pred, vxg_canoni
     uint64_t k = 0;
     VXG_TRY(hip_check(hipMemcpyAsync(&k, to + tiles, 8, hipMemcpyDeviceToHost, s_), "filter count readback"));
     VXG_TRY(hip_check(hipStreamSynchronize(s_), "filter count sync"));
+    VXG_TRY(filter_selected(a, m, to, k, out, nullptr));
+    // strings: complete on return, like the reference's compute::filter
+    return is_str ? hip_check(hipStreamSynchronize(s_), "filter sync") : VXG_OK;
+}
 
+// The part of compute::filter after the count: `a` canonicalized into temporaries and compacted by
+// the mask `m` (whole u64 words; bits past len are ignored) with its scanned tile offsets `to` and
+// true count `k`.  A string array waits once for its heap size (*syncs counts it); the heap's bytes
+// are enqueued like every other output.
+vxg_status Planner::filter_selected(const vxg_array& a, const uint64_t* m, const uint64_t* to, uint64_t k,
+                                    vxg_canonical& out, uint32_t* syncs) {
+    const bool is_str = is_string(a);
+    const uint64_t n = a.len;
     // canonical source in temporaries
     vxg_canonical src{};
     const vxg_array* vnode;
@@ -1272,10 +1285,21 @@ vxg_status Planner::filter(const vxg_array& a, const vxg_array& pred, vxg_canoni
     uint8_t* views = static_cast<uint8_t*>(out.views);
     const uint8_t* valid = static_cast<const uint8_t*>(out.validity);
     VXG_TRY(launch_view_heap_sizes(views, k, valid, static_cast<uint64_t*>(hoff), s_));
+    // the table of the source buffers goes up before the heap-size readback, whose sync drains
+    // the copy: `bases` is not read after it
+    std::vector<const uint8_t*> bases(bufs.size());
+    for (size_t i = 0; i < bufs.size(); ++i) bases[i] = static_cast<const uint8_t*>(src.data) + bufs[i].offset;
+    void* dbases;
+    VXG_TRY(temp(bases.size() * sizeof(void*) + 8, &dbases));
+    if (!bases.empty())
+        VXG_TRY(hip_check(hipMemcpyAsync(dbases, bases.data(), bases.size() * sizeof(void*), hipMemcpyHostToDevice, s_),
+                          "filter buffer table upload"));
     uint64_t heap = 0;
-    VXG_TRY(hip_check(hipMemcpyAsync(&heap, static_cast<uint64_t*>(hoff) + ktiles, 8, hipMemcpyDeviceToHost, s_),
-                      "filter heap readback"));
+    const vxg_status rb = hip_check(hipMemcpyAsync(&heap, static_cast<uint64_t*>(hoff) + ktiles, 8, hipMemcpyDeviceToHost, s_),
+                                    "filter heap readback");
     VXG_TRY(hip_check(hipStreamSynchronize(s_), "filter heap sync"));
+    VXG_TRY(rb);
+    if (syncs) ++*syncs;
     if (heap > 0xFFFFFFFFull) return set_error(VXG_ERR_INVALID_ARGUMENT, "filtered string heap exceeds u32 view offsets");
     if (out.data && out.data_bytes < heap)
         return set_error(VXG_ERR_INVALID_ARGUMENT, "caller-provided data holds " + std::to_string(out.data_bytes) +
@@ -1284,17 +1308,201 @@ vxg_status Planner::filter(const vxg_array& a, const vxg_array& pred, vxg_canoni
     out.data_bytes = heap;
     out.n_data_buffers = 1;
     if (out.data_buffers && out.data_buffers_cap >= 1) out.data_buffers[0] = vxg_data_buffer{0, heap};
-    std::vector<const uint8_t*> bases(bufs.size());
-    for (size_t i = 0; i < bufs.size(); ++i) bases[i] = static_cast<const uint8_t*>(src.data) + bufs[i].offset;
-    void* dbases;
-    VXG_TRY(temp(bases.size() * sizeof(void*) + 8, &dbases));
-    if (!bases.empty())
-        VXG_TRY(hip_check(hipMemcpyAsync(dbases, bases.data(), bases.size() * sizeof(void*), hipMemcpyHostToDevice, s_),
-                          "filter buffer table upload"));
-    VXG_TRY(launch_view_heap_build(views, k, valid, static_cast<uint64_t*>(hoff),
-                                   static_cast<const uint8_t* const*>(dbases), uint32_t(bases.size()),
-                                   static_cast<uint8_t*>(out.data), ctx_->c.err_word, s_));
-    return hip_check(hipStreamSynchronize(s_), "filter sync");  // `bases` is read by the upload
+    return launch_view_heap_build(views, k, valid, static_cast<uint64_t*>(hoff),
+                                  static_cast<const uint8_t* const*>(dbases), uint32_t(bases.size()),
+                                  static_cast<uint8_t*>(out.data), ctx_->c.err_word, s_);
+}
+
+// ---- filter(batch, mask): the scan's last step (vortex-serde layouts/read/stream.rs:143-149) ----
+// One mask for every column of the batch: counted and scanned once, k read back once.  Per column
+// (classified and validated before the first launch):
+//   Packed    BitPacked / FoR(BitPacked) / ZigZag / ALP over either (compare_shape), or a top-level
+//             Chunked whose non-empty chunks all have such a shape: K22 reads the packed words and
+//             writes only the selected rows; chunks of one (T, epilogue) share a launch;
+//   InPlace   a Primitive array, or a Chunked of Primitive chunks: compacted from its own buffers;
+//   Fallback  everything else, and VXG_FILTB_CANONICALIZE: filter_selected (canonicalize, compact).
+// The validity of every route is validity_into a temporary, then launch_filter_bits.
+vxg_status Planner::filter_batch(const vxg_array* const* cols, uint32_t n_cols, const void* mask, uint64_t n,
+                                 uint32_t flags, vxg_canonical* outs, uint64_t* true_count, vxg_filter_batch_info& info) {
+    enum class Route { Packed, InPlace, Fallback };
+    struct Col {
+        Route route = Route::Fallback;
+        std::vector<CmpFused> fused;                              // Packed: the non-empty arrays/chunks
+        std::vector<std::pair<const void*, uint64_t>> prims;      // InPlace: buffer, first row
+        std::vector<uint64_t> prim_len;
+        int vkind = 0;
+    };
+    const bool force = (flags & VXG_FILTB_CANONICALIZE) != 0;
+    info.columns = n_cols;
+    std::vector<Col> plan(n_cols);
+    for (uint32_t ci = 0; ci < n_cols; ci++) {
+        const vxg_array& a = *cols[ci];
+        Col& col = plan[ci];
+        const vxg_array* vnode;
+        VXG_TRY(validity_source(a, &vnode, &col.vkind));
+        if (a.dtype != VXG_DTYPE_PRIMITIVE || width(a) == 0 || n == 0) continue;  // Bool, strings: Fallback
+        // the pieces: the array itself, or the non-empty chunks of a top-level Chunked at their first rows
+        std::vector<std::pair<const vxg_array*, uint64_t>> pieces;
+        if (a.encoding == VXG_ENC_CHUNKED) {
+            if (a.n_children != a.meta.chunked.nchunks + 1)
+                return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked child count != nchunks + 1");
+            uint64_t off = 0;
+            for (uint32_t i = 1; i < a.n_children; i++) {
+                const vxg_array& c = a.children[i];
+                if (c.dtype != a.dtype || c.ptype != a.ptype)
+                    return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the same dtype");
+                if (c.len) pieces.emplace_back(&c, off);
+                off += c.len;
+            }
+            if (off != n) return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked chunk lengths do not sum to len");
+        } else {
+            pieces.emplace_back(&a, 0);
+        }
+        // compare_shape's checks run for every piece, whatever route the column then takes
+        size_t n_fused = 0, n_prim = 0;
+        bool misaligned = false;
+        for (const auto& [p, row] : pieces) {
+            CmpFused f;
+            bool is_fused;
+            VXG_TRY(compare_shape(*p, row, f, &is_fused));
+            if (is_fused) {
+                col.fused.push_back(f);
+                n_fused++;
+            } else if (p->encoding == VXG_ENC_PRIMITIVE) {
+                const void* pv;
+                VXG_TRY(view_primitive(*p, &pv));  // (a Primitive array: its own buffer, nothing is decoded)
+                misaligned = misaligned || reinterpret_cast<uintptr_t>(pv) % uint64_t(width(a));
+                col.prims.emplace_back(pv, row);
+                col.prim_len.push_back(p->len);
+                n_prim++;
+            }
+        }
+        if (force) continue;
+        if (n_fused == pieces.size()) col.route = Route::Packed;
+        else if (n_prim == pieces.size()) col.route = Route::InPlace;
+        if (col.route == Route::InPlace && misaligned)  // (as compare_impl checks the buffers it reads in place)
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "primitive buffer must be aligned to the value width");
+        if (col.route != Route::Fallback && (reinterpret_cast<uintptr_t>(outs[ci].values) % uint64_t(width(a))))
+            return set_error(VXG_ERR_INVALID_ARGUMENT, "filter output must be aligned to the value width");
+    }
+
+    // the one count + scan of the mask, and the one readback of k
+    const uint64_t tiles = filter_tiles(n);
+    const uint64_t* m = static_cast<const uint64_t*>(mask);
+    uint64_t* to = nullptr;
+    uint64_t k = 0;
+    if (n) {
+        void* toff;
+        VXG_TRY(temp((tiles + 1) * 8, &toff));
+        to = static_cast<uint64_t*>(toff);
+        VXG_TRY(launch_filter_count(m, n, to, s_));
+        info.mask_scans = 1;
+        const vxg_status rb = hip_check(hipMemcpyAsync(&k, to + tiles, 8, hipMemcpyDeviceToHost, s_), "filter count readback");
+        VXG_TRY(hip_check(hipStreamSynchronize(s_), "filter count sync"));
+        VXG_TRY(rb);
+        info.syncs++;
+    }
+    if (true_count) *true_count = k;
+    const FiltMask fm{m, n, to, k};
+
+    for (uint32_t ci = 0; ci < n_cols; ci++) {
+        const vxg_array& a = *cols[ci];
+        Col& col = plan[ci];
+        vxg_canonical& out = outs[ci];
+        if (k == 0) {  // the scan's skip (stream.rs:144-146): nothing is launched or allocated
+            out.kind = is_string(a) ? VXG_ENC_VARBINVIEW : a.dtype == VXG_DTYPE_BOOL ? VXG_ENC_BOOL : VXG_ENC_PRIMITIVE;
+            out.len = 0;
+            out.dtype = a.dtype;
+            out.ptype = a.ptype;
+            out.values_bytes = 0;
+            if (col.vkind == 0) out.validity = nullptr;
+            if (is_string(a)) {
+                out.data_bytes = 0;
+                out.n_data_buffers = 1;
+                if (out.data_buffers && out.data_buffers_cap >= 1) out.data_buffers[0] = vxg_data_buffer{0, 0};
+            }
+            continue;
+        }
+        if (col.route == Route::Fallback) {
+            info.fallback_arrays++;
+            VXG_TRY(filter_selected(a, m, to, k, out, &info.syncs));
+            continue;
+        }
+        out.kind = VXG_ENC_PRIMITIVE;
+        out.len = k;
+        out.dtype = a.dtype;
+        out.ptype = a.ptype;
+        out.values_bytes = k * width(a);
+        const uint64_t vbits = ((k + 31) / 32) * 4;
+        if (col.vkind != 0) {  // validity.filter(mask)
+            void* src = nullptr;
+            VXG_TRY(temp(((n + 31) / 32) * 4, &src));
+            VXG_TRY(validity_into(a, &src));
+            if (!out.validity) VXG_TRY(hip_check(hipMalloc(&out.validity, vbits), "filter validity alloc"));
+            VXG_TRY(launch_copy_bytes(out.validity, nullptr, vbits, s_));
+            VXG_TRY(launch_filter_bits(m, n, to, static_cast<const uint8_t*>(src), out.validity, s_));
+        } else {
+            out.validity = nullptr;
+        }
+        if (!out.values) VXG_TRY(hip_check(hipMalloc(&out.values, out.values_bytes), "filter values alloc"));
+        if (col.route == Route::InPlace) {
+            for (size_t i = 0; i < col.prims.size(); i++) {
+                VXG_TRY(launch_filter_range(width(a), col.prims[i].first, col.prims[i].second, col.prim_len[i], fm,
+                                            out.values, s_));
+                info.inplace_arrays++;
+            }
+            continue;
+        }
+        // Packed: one launch per (T, epilogue) and kCmpArgChunks chunks, the table as the argument
+        std::vector<CmpFused*> order;
+        for (CmpFused& f : col.fused) order.push_back(&f);
+        std::stable_sort(order.begin(), order.end(), [](const CmpFused* x, const CmpFused* y) {
+            return std::make_tuple(x->T, int(x->epi)) < std::make_tuple(y->T, int(y->epi));
+        });
+        for (size_t i = 0; i < order.size();) {
+            size_t j = i;
+            uint64_t blocks = 0;
+            while (j < order.size() && j - i < size_t(kCmpArgChunks) && order[j]->T == order[i]->T &&
+                   order[j]->epi == order[i]->epi)
+                blocks += order[j++]->d.n_blocks();
+            // small launches take fewer blocks per workgroup (>= 4: one per wave), the compare's rule
+            uint32_t pick = uint32_t(std::min<uint64_t>(32, blocks / 1024)) & ~3u;
+            if (pick < 4) pick = 4;
+            CmpTable tab{};
+            uint64_t groups = 0;
+            uint32_t lds = 0;
+            for (size_t x = i; x < j; x++) {
+                CmpChunk& c = tab.c[tab.n++];
+                c = order[x]->d;
+                const uint32_t bpw = std::min(cmp_bpw_max(c.W), pick);
+                c.bpw_excl = uint8_t(bpw);
+                c.first_group = uint32_t(groups);
+                groups += (c.n_blocks() + bpw - 1) / bpw;
+                lds = std::max(lds, bpw * 128u * c.W);
+            }
+            // (+ one word row of slack: a value's second word is read unconditionally)
+            VXG_TRY(launch_filter_packed(order[i]->T, order[i]->epi, tab, groups, lds + 128, fm, out.values, s_));
+            info.packed_launches++;
+            info.packed_chunks += uint32_t(j - i);
+            i = j;
+        }
+        // patched rows: BitPacked's raw values through the epilogue, then ALP's values as they are
+        for (const CmpFused& f : col.fused) {
+            if (f.bp->meta.bitpacked.has_patches) {
+                TakePatches tp;
+                VXG_TRY(take_patches(*child(*f.bp, 0), tp));
+                VXG_TRY(launch_filter_patch(f.T, f.epi, tp, f.d.len(), f.d.out_bit, f.ep, fm, out.values, s_));
+                info.patch_launches += tp.n != 0;
+            }
+            if (f.outer) {
+                TakePatches tp;
+                VXG_TRY(take_patches(*f.outer, tp));
+                VXG_TRY(launch_filter_patch_raw(width(a), tp, f.d.len(), f.d.out_bit, fm, out.values, ctx_->c.err_word, s_));
+                info.patch_launches += tp.n != 0;
+            }
+        }
+    }
+    return VXG_OK;
 }
 
 }  // namespace vxg
