@@ -385,6 +385,34 @@ def slice_bitpacked(a: Array, start: int, stop: int) -> Array:
     return A.bitpacked(packed, a.ptype, W, stop - start, offset, patches, validity=_slice_validity(a, start, stop))
 
 
+def bad_bitpacked(bp: Array):
+    """The three rejections of BitPackedArray::try_new_from_offset (bitpacking/mod.rs:54-130) on a
+    one-block (1024-row) BitPacked array -> [(malformed copy, a substring of the error text)]: offset
+    1024, a bit width one above the type's, a packed buffer one block short."""
+    import dataclasses
+    T, W = 8 * ptype_width(bp.ptype), bp.meta["bit_width"]
+    assert bp.encoding == ENC["FL_BITPACKED"] and bp.len == 1024 and bp.meta["offset"] == 0 and W > 0
+    return [
+        (dataclasses.replace(bp, meta=dict(bp.meta, offset=1024)), "Offset must be less than full block"),
+        (dataclasses.replace(bp, meta=dict(bp.meta, bit_width=T + 1)), "Unsupported bit width"),
+        (dataclasses.replace(bp, buffers=[np.asarray(bp.buffers[0])[:-128 * W]]),
+         f"Expected {128 * W} packed bytes, got 0"),
+    ]
+
+
+def misaligned_bitpacked(bp: Array, device) -> Array:
+    """`bp` with its packed bytes in device memory 4 bytes past a 16-byte boundary (Array.to keeps a
+    device tensor where it lies)."""
+    import dataclasses
+
+    import torch
+    src = torch.from_numpy(np.ascontiguousarray(bp.buffers[0]).view(np.uint8).copy())
+    t = torch.zeros(src.numel() + 16, dtype=torch.uint8, device=device)
+    assert t.data_ptr() % 16 == 0
+    t[4:4 + src.numel()].copy_(src)
+    return dataclasses.replace(bp, buffers=[t[4:4 + src.numel()]])
+
+
 def _slice_validity(a: Array, start: int, stop: int):
     """Validity::slice (validity.rs): the metadata kinds stay, an Array child is sliced -- a
     BoolArray child by slice_bool (its bit offset moves), any other Bool encoding as its bits."""

@@ -14,7 +14,7 @@ import vortex_amd._lib as L
 import vortex_amd.arrays as A
 import vortex_amd.encode as E
 from compare_expected import OPS, bitmap, expected
-from oracle_tree import canon, slice_bitpacked
+from oracle_tree import bad_bitpacked, canon, misaligned_bitpacked, slice_bitpacked
 
 pytestmark = pytest.mark.gpu
 
@@ -357,6 +357,11 @@ def test_errors(ctx):
     short = dataclasses.replace(ok, buffers=[np.asarray(ok.buffers[0])[:-128]])
     assert _status(ctx, short) == "InvalidArgument"
     assert "Expected 896 packed bytes, got 768" in ctx.lib.vxg_last_error().decode()
+    # the BitPacked leaf of a FoR, malformed: rejected before anything is launched
+    block = E.encode_bitpacked(np.arange(1024, dtype=np.uint32) % 128, bit_width=7, allow_patches=False)
+    for bad, text in bad_bitpacked(block) + [(misaligned_bitpacked(block, _dev()), "16-byte aligned")]:
+        assert _status(ctx, A.frame_of_reference(bad, 5, 0, "u32")) == "InvalidArgument"
+        assert text in ctx.lib.vxg_last_error().decode()
     with pytest.raises(V.VortexGpuError, match="unknown operator"):
         V.compare(ok.to(_dev()), "~", 1, ctx)
 

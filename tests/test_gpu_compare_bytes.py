@@ -16,7 +16,7 @@ import vortex_amd.arrays as A
 import vortex_amd.encode as E
 from compare_bytes_expected import expected, rows_of
 from compare_expected import OPS
-from oracle_tree import slice_bitpacked
+from oracle_tree import bad_bitpacked, misaligned_bitpacked, slice_bitpacked
 
 pytestmark = pytest.mark.gpu
 
@@ -393,6 +393,12 @@ def test_errors(ctx):
         codes, buffers=[np.asarray(codes.buffers[0])[:-128]])])
     assert _status(ctx, short) == "InvalidArgument"
     assert "Expected 256 packed bytes, got 128" in ctx.lib.vxg_last_error().decode()
+    # the BitPacked codes of a Dict, malformed: rejected before anything is launched
+    block = E.encode_dict_strings([b"AIR", b"MAIL"] * 512)
+    values, codes = block.children
+    for bad, text in bad_bitpacked(codes) + [(misaligned_bitpacked(codes, _dev()), "16-byte aligned")]:
+        assert _status(ctx, dataclasses.replace(block, children=[values, bad])) == "InvalidArgument"
+        assert text in ctx.lib.vxg_last_error().decode()
     with pytest.raises(V.VortexGpuError, match="unknown operator"):
         V.compare(ok.to(_dev()), "~", b"AIR", ctx)
 

@@ -13,7 +13,7 @@ import vortex_amd as V
 import vortex_amd._lib as L
 import vortex_amd.arrays as A
 import vortex_amd.encode as E
-from oracle_tree import filter_canon, slice_bitpacked
+from oracle_tree import bad_bitpacked, filter_canon, slice_bitpacked
 
 pytestmark = pytest.mark.gpu
 
@@ -485,6 +485,12 @@ def test_errors(ctx):
     assert "16-byte aligned" in ctx.lib.vxg_last_error().decode()
     # ... and under VXG_FILTB_CANONICALIZE too
     assert _call(ctx, [good, bad_bytes], mp, n, flags=CANON) == INVALID
+    # every rejection of a BitPacked buffer, on the leaf of a FoR of one block
+    block = E.encode_bitpacked(np.arange(1024, dtype=np.uint32) % 128, bit_width=7, allow_patches=False)
+    for bad, text in bad_bitpacked(block):
+        node = A.flatten(A.frame_of_reference(bad, 5, 0, "u32").to(_dev()), keep)
+        assert _call(ctx, [node], mp, 1024) == INVALID
+        assert text in ctx.lib.vxg_last_error().decode()
 
 
 def test_good_call_allocates_what_is_null(ctx):

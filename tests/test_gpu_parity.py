@@ -14,7 +14,7 @@ import pytest
 import vortex_amd as V
 import vortex_amd.arrays as A
 import vortex_amd.encode as E
-from oracle_tree import canon, view_bytes
+from oracle_tree import bad_bitpacked, canon, misaligned_bitpacked, view_bytes
 from plan_env import env_set, plan_mode
 
 pytestmark = pytest.mark.gpu
@@ -1000,6 +1000,21 @@ def test_direct_bitunpack_entry(ctx):
     st = lib.vxg_bitunpack(ctx.handle, V.PTYPE["u32"], 7, 0, vals.size + 5000, C.c_void_p(dp.data_ptr()),
                            packed.size, C.c_void_p(out.data_ptr()), ctx.stream_ptr())
     assert st == 3 and b"packed bytes" in lib.vxg_last_error()
+
+
+def test_bitpacked_buffer_is_validated(ctx):
+    """BitPackedArray::try_new_from_offset's rejections (bitpacking/mod.rs:54-130) before anything is
+    launched: canonicalize of the array itself, and of a RunEnd that reads packed ends in place."""
+    block = E.encode_bitpacked(np.arange(1, 1025, dtype=np.uint32), bit_width=11, allow_patches=False)
+    values = A.primitive(np.arange(1024, dtype=np.int32))
+    for bad, text in bad_bitpacked(block) + [(misaligned_bitpacked(block, torch_dev()), "16-byte aligned")]:
+        with pytest.raises(V.VortexGpuError, match=text) as ei:
+            gpu(bad, ctx)
+        assert ei.value.kind == "InvalidArgument"
+    for bad, text in bad_bitpacked(block):  # (runs of one row: the short-run kernel's packed ends)
+        with pytest.raises(V.VortexGpuError, match=text) as ei:
+            gpu(A.run_end(bad, values, length=1024), ctx)
+        assert ei.value.kind == "InvalidArgument"
 
 
 def _bench():
@@ -2178,6 +2193,12 @@ def test_take_validity_and_errors(ctx):
         A.take(E.encode_bitpacked(v, bit_width=12, allow_patches=False).to(torch_dev()),
                np.array([1, n], np.uint32), ctx)
     assert ei.value.kind == "OutOfBounds"
+    # a malformed BitPacked buffer is rejected before the take is launched
+    block = E.encode_bitpacked(v[:1024], bit_width=12, allow_patches=False)
+    for bad, text in bad_bitpacked(block):
+        with pytest.raises(V.VortexGpuError, match=text) as ei:
+            A.take(bad.to(torch_dev()), np.array([3], np.uint32), ctx)
+        assert ei.value.kind == "InvalidArgument"
 
 
 @pytest.mark.parametrize("dt", [np.int8, np.int16, np.int32, np.int64])

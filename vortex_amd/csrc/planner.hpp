@@ -14,9 +14,11 @@
 // Which K1 kernel a launch takes is one rule, k1_choose (vxg_internal.hpp): launch_one switches on
 // it and decode_alp asks it beforehand whether the launch will write its outer patches.
 //
-// Units: planner_launch.hip (launch grouping, K1 dispatch), planner_decode.hip (primitives,
-// validity, bools, canonical()), planner_strings.hip, planner_compute.hip (take, filter, compare),
-// plan.hip (the plan recorder), capi.hip (the context and the C entry points).
+// Units: planner_launch.hip (launch grouping, K1 dispatch, the BitPacked buffer check),
+// planner_decode.hip (primitives, validity, bools, canonical(), the cascade classifier),
+// planner_strings.hip (string canonicalize, the string readers), planner_take.hip,
+// planner_compare.hip (compare, compare_bytes, row_filter), planner_filter.hip (filter,
+// filter_batch), plan.hip (the plan recorder), capi.hip (the context and the C entry points).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -26,6 +28,7 @@
 #include <utility>
 #include <vector>
 
+#include "chunk_pack.hpp"
 #include "compare.hpp"
 #include "compare_str.hpp"
 #include "env.hpp"
@@ -75,7 +78,12 @@ struct PlanBatch {
 };
 
 // ---- launch grouping (planner_launch.hip) ---------------------------------------------------
-// Validate one BitPacked buffer (bitpacking/mod.rs:54-130) and describe its K1 decode.
+// Validate one BitPacked buffer (bitpacking/mod.rs:54-130): the slice offset, the bit width against
+// the type's T bits, the byte count of the 1024-row blocks and, for the kernels that read 16-byte
+// words (`aligned`), the pointer.  *nblk: the blocks that len + offset rows cover.
+vxg_status check_bitpacked(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
+                           bool aligned, uint64_t* nblk);
+// check_bitpacked (aligned), then describe the buffer's K1 decode.
 vxg_status make_k1_job(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
                        Epi epi, int vw, const UnpackArgs& a, void* out, K1Job& j);
 // K1 jobs launched now, grouped by kernel; dt: the plan being recorded, or null; patch: the outer
@@ -194,6 +202,27 @@ class Planner {
     // validated; otherwise *packed = false and nothing is decoded
     vxg_status packed_column(const vxg_array& a, IntCol& c, bool* packed);
     vxg_status runend_column(const vxg_array& a, bool in_place, IntCol& c);
+    // `c` is FoR(BitPacked) or BitPacked: the BitPacked leaf, with the FoR's reference and shift
+    // (left as they are for a bare BitPacked); anything else: null.
+    const vxg_array* fl_leaf(const vxg_array* c, uint64_t* reference, uint32_t* shift) const;
+    // ALP's decode factors F10[f] and IF10[e] of an f32 / f64 array (alp/compress.rs:61-78); false
+    // when an exponent lies outside the ptype's table.
+    static bool alp_factors(const vxg_array& a, double* alp_a, double* alp_b);
+    // A BitPacked-rooted cascade that one fused kernel serves -- BitPacked, FoR(BitPacked), ZigZag or
+    // ALP over either, the leaf of the array's own width and length -- with its packed buffer
+    // validated (check_bitpacked).  take, compare and filter_batch build their kernel arguments
+    // from it.
+    struct Cascade {
+        const vxg_array* bp = nullptr;     // the BitPacked leaf; null: not a served shape
+        const vxg_array* outer = nullptr;  // ALP's patches, named even where the shape is not served
+        int T = 0;                         // bits of the leaf's type
+        Epi epi = Epi::Plain;
+        EpiParams ep{};                    // reference, shift, alp_a, alp_b
+        const uint8_t* packed = nullptr;
+        unsigned W = 0, offset = 0;
+    };
+    // `aligned`: the kernel reads the packed buffer in 16-byte words
+    vxg_status classify_cascade(const vxg_array& a, bool aligned, Cascade& c);
 
     // A BitPacked array under the epilogue of its parents: validate it and describe its K1 decode
     // (*patches: its patches child, or null), then queue the decode into `sink` or, without one,
@@ -223,23 +252,58 @@ class Planner {
     vxg_status take_strings(const vxg_array& a, const void* idx, int iw, bool isg, uint64_t n, bool force,
                             vxg_canonical& out, vxg_take_info& info);
     vxg_status take_patches(const vxg_array& sp, TakePatches& p);
-    // A BitPacked-rooted cascade the fused compare kernel serves, validated (compare).
-    struct CmpFused {
+    // A cascade the fused compare kernel serves (compare, filter_batch): the launch's share
+    // (CmpJob, chunk_pack.hpp) and what the patch launches after it need.
+    struct CmpFused : CmpJob {
         const vxg_array* arr;    // the array or chunk
         const vxg_array* bp;     // its BitPacked leaf
         const vxg_array* outer;  // ALP patches, or null
-        int T, ck;
-        Epi epi;
         EpiParams ep;
-        CmpChunk d;
-        bool excl;
     };
     vxg_status compare_shape(const vxg_array& a, uint64_t out_bit, CmpFused& f, bool* fused);
-    vxg_status launch_compare_group(std::vector<CmpFused*>& group, void* out, uint64_t scalar_bits, int op,
-                                    const CmpRange* range);
     // compare(); with `range`, both tests of a range in the same walk and launches
     vxg_status compare_impl(const vxg_array& a, int op, uint64_t scalar_bits, const CmpRange* range, uint32_t flags,
                             vxg_canonical& out, vxg_compare_info& info);
+    // The pieces of a compute call with their first rows: `a` itself, or the chunks of a top-level
+    // Chunked (check_ptype: of a's ptype as well as its dtype; skip_empty: only those with rows).
+    using Pieces = std::vector<std::pair<const vxg_array*, uint64_t>>;
+    vxg_status chunk_pieces(const vxg_array& a, bool check_ptype, bool skip_empty, Pieces& pieces);
+    // The header and value bitmap (whole u64 words, 8-byte aligned) of an n-row Bool result;
+    // `what` names the call in the error texts.
+    vxg_status bool_output(uint64_t n, const char* what, vxg_canonical& out);
+    // The end of a compare: the value bits of null rows cleared and, unless null_as_false, the
+    // validity handed out.
+    vxg_status compare_validity(const vxg_array& a, uint32_t flags, vxg_canonical& out);
+    // The children of a VarBin / VarBinView / FSST array, checked and read where they lie.
+    struct VarBinSrc {
+        const uint8_t* bytes;
+        uint64_t bytes_len;
+        CCol offs;
+    };
+    struct ViewSrc {
+        const uint8_t* views;  // 16-byte aligned
+        std::vector<StrBuf> bufs;
+    };
+    struct FsstSrc {
+        const uint64_t* symbols;
+        const uint8_t* sym_lens;
+        const uint8_t* codes;
+        uint64_t codes_len;
+        CCol offs, lens;
+        uint32_t n_symbols;
+    };
+    vxg_status string_bytes(const vxg_array& b, const void** p);
+    vxg_status read_varbin(const vxg_array& s, VarBinSrc& v);
+    vxg_status read_varbinview(const vxg_array& s, ViewSrc& v);
+    vxg_status read_fsst(const vxg_array& s, FsstSrc& f);
+    // The canonical of string array `s` in temporaries: src.views, src.data under the layout `lay`
+    // (src.data_buffers points into it) and src.validity (null: no nulls).
+    vxg_status string_canonical_temp(const vxg_array& s, vxg_canonical& src, std::vector<vxg_data_buffer>& lay);
+    // The one heap of a take's or filter's string result, its size known: checked against the
+    // caller's buffer or allocated.  op / rows name the call in the error texts ("take" / "taken").
+    vxg_status size_string_heap(vxg_canonical& out, uint64_t heap, const char* op, const char* rows);
+    // One u64 from device memory, waited for; `what` names it in the error texts.
+    vxg_status read_u64(const uint64_t* dev, const char* what, uint64_t* v);
     // The string pieces of one row-compare target (the output bitmap, or the truth tables of the
     // Dict pieces), by kernel.
     struct StrRows {

@@ -58,31 +58,93 @@ vxg_status Planner::packed_column(const vxg_array& a, IntCol& c, bool* packed) {
     c = IntCol{};
     c.width = width(a);
     c.sgn = ptype_is_signed(a.ptype);
-    const vxg_array* bp = nullptr;
-    if (a.encoding == VXG_ENC_FL_FOR && child(a, 0) && child(a, 0)->encoding == VXG_ENC_FL_BITPACKED) {
-        bp = child(a, 0);
-        c.reference = a.meta.for_.reference;
-        c.shift = a.meta.for_.shift;
-    } else if (a.encoding == VXG_ENC_FL_BITPACKED) {
-        bp = &a;
-    }
+    const vxg_array* bp = fl_leaf(&a, &c.reference, &c.shift);
     if (bp && !bp->meta.bitpacked.has_patches && width(*bp) == c.width && (c.width == 4 || c.width == 8) &&
         bp->len == a.len) {
         const vxg_buffer* pk = buf(*bp, 0);
-        const unsigned W = bp->meta.bitpacked.bit_width, off = bp->meta.bitpacked.offset;
-        const uint64_t nblk = (bp->len + off + 1023) / 1024;
-        if (off > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
-        if (W > unsigned(8 * c.width)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
-        const uint64_t have = pk ? pk->len : 0;
-        if (W > 0 && have != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
-            return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
-                                                           " packed bytes, got " + std::to_string(have));
+        uint64_t nblk;  // (elements are unpacked one by one: no alignment is asked for)
+        VXG_TRY(check_bitpacked(8 * c.width, bp->meta.bitpacked.bit_width, bp->meta.bitpacked.offset, bp->len,
+                                pk ? pk->ptr : nullptr, pk ? pk->len : 0, false, &nblk));
         c.packed = true;
         c.p = pk ? pk->ptr : nullptr;
-        c.W = W;
-        c.offset = off;
+        c.W = bp->meta.bitpacked.bit_width;
+        c.offset = bp->meta.bitpacked.offset;
         *packed = true;
     }
+    return VXG_OK;
+}
+
+const vxg_array* Planner::fl_leaf(const vxg_array* c, uint64_t* reference, uint32_t* shift) const {
+    if (c && c->encoding == VXG_ENC_FL_FOR && child(*c, 0) && child(*c, 0)->encoding == VXG_ENC_FL_BITPACKED) {
+        *reference = c->meta.for_.reference;
+        *shift = c->meta.for_.shift;
+        return child(*c, 0);
+    }
+    return c && c->encoding == VXG_ENC_FL_BITPACKED ? c : nullptr;
+}
+
+bool Planner::alp_factors(const vxg_array& a, double* alp_a, double* alp_b) {
+    const bool f32 = a.ptype == VXG_F32;
+    const unsigned e = a.meta.alp.e, f = a.meta.alp.f, top = f32 ? 10 : 23;
+    if ((!f32 && a.ptype != VXG_F64) || e > top || f > top) return false;
+    *alp_a = f32 ? double(kF10f[f]) : kF10d[f];
+    *alp_b = f32 ? double(kIF10f[e]) : kIF10d[e];
+    return true;
+}
+
+vxg_status Planner::classify_cascade(const vxg_array& a, bool aligned, Cascade& c) {
+    c = Cascade{};
+    const vxg_array* bp = nullptr;
+    switch (a.encoding) {
+    case VXG_ENC_FL_BITPACKED: bp = &a; break;  // bitpacking/compute/take.rs:21-125
+    case VXG_ENC_FL_FOR:                          // for/compute.rs:39-48: the child, under the FoR
+        bp = fl_leaf(&a, &c.ep.reference, &c.ep.shift);
+        c.epi = Epi::For;
+        break;
+    case VXG_ENC_ZIGZAG:  // zigzag/compute.rs: the encoded child, decoded
+        bp = fl_leaf(child(a, 0), &c.ep.reference, &c.ep.shift);
+        c.epi = Epi::ForZigZag;
+        break;
+    case VXG_ENC_ALP:  // alp/compute.rs: the encoded child and the patches
+        if (!alp_factors(a, &c.ep.alp_a, &c.ep.alp_b)) return VXG_OK;
+        bp = fl_leaf(child(a, 0), &c.ep.reference, &c.ep.shift);
+        c.epi = a.ptype == VXG_F32 ? Epi::AlpF32 : Epi::AlpF64;
+        if (bp && a.meta.alp.has_patches) {
+            if (!child(a, 1)) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: patches child missing");
+            c.outer = child(a, 1);
+        }
+        break;
+    default: return VXG_OK;
+    }
+    if (!bp || width(*bp) != width(a) || bp->len != a.len) return VXG_OK;
+    const vxg_buffer* pb = buf(*bp, 0);
+    c.T = 8 * width(*bp);
+    c.W = bp->meta.bitpacked.bit_width;
+    c.offset = bp->meta.bitpacked.offset;
+    uint64_t nblk;
+    VXG_TRY(check_bitpacked(c.T, c.W, c.offset, bp->len, pb ? pb->ptr : nullptr, pb ? pb->len : 0, aligned, &nblk));
+    c.packed = pb ? static_cast<const uint8_t*>(pb->ptr) : nullptr;
+    c.bp = bp;
+    return VXG_OK;
+}
+
+vxg_status Planner::chunk_pieces(const vxg_array& a, bool check_ptype, bool skip_empty, Pieces& pieces) {
+    if (a.encoding != VXG_ENC_CHUNKED) {
+        pieces.emplace_back(&a, 0);
+        return VXG_OK;
+    }
+    if (a.n_children != a.meta.chunked.nchunks + 1)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked child count != nchunks + 1");
+    pieces.reserve(a.n_children);
+    uint64_t off = 0;
+    for (uint32_t i = 1; i < a.n_children; i++) {
+        const vxg_array& c = a.children[i];
+        if (c.dtype != a.dtype || (check_ptype && c.ptype != a.ptype))
+            return set_error(VXG_ERR_MISMATCHED_TYPES, "Chunks must have the same dtype");
+        if (c.len || !skip_empty) pieces.emplace_back(&c, off);
+        off += c.len;
+    }
+    if (off != a.len) return set_error(VXG_ERR_INVALID_ARGUMENT, "Chunked chunk lengths do not sum to len");
     return VXG_OK;
 }
 
@@ -158,22 +220,10 @@ vxg_status Planner::decode_alp(const vxg_array& a, void* dst, K1Sink* sink) {
     if (!enc) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALPArray: encoded child missing");
     const bool f32 = a.ptype == VXG_F32;
     if (!f32 && a.ptype != VXG_F64) return set_error(VXG_ERR_MISMATCHED_TYPES, "ALP can only encode f32 and f64");
-    const unsigned e = a.meta.alp.e, f = a.meta.alp.f;
-    if ((f32 && (e > 10 || f > 10)) || (!f32 && (e > 23 || f > 23)))
-        return set_error(VXG_ERR_INVALID_ARGUMENT, "ALP exponents out of range");
     UnpackArgs ua{};
-    ua.alp_a = f32 ? double(kF10f[f]) : kF10d[f];
-    ua.alp_b = f32 ? double(kIF10f[e]) : kIF10d[e];
+    if (!alp_factors(a, &ua.alp_a, &ua.alp_b)) return set_error(VXG_ERR_INVALID_ARGUMENT, "ALP exponents out of range");
     const Epi epi = f32 ? Epi::AlpF32 : Epi::AlpF64;
-    const vxg_array* bp = nullptr;
-    if (enc->encoding == VXG_ENC_FL_FOR && child(*enc, 0) &&
-        child(*enc, 0)->encoding == VXG_ENC_FL_BITPACKED) {
-        ua.reference = enc->meta.for_.reference;
-        ua.shift = enc->meta.for_.shift;
-        bp = child(*enc, 0);
-    } else if (enc->encoding == VXG_ENC_FL_BITPACKED) {
-        bp = enc;
-    }
+    const vxg_array* bp = fl_leaf(enc, &ua.reference, &ua.shift);
     bool fused = false;  // the outer patches written by the K1w launch itself
     if (bp && width(*bp) == (f32 ? 4 : 8)) {
         PatchCol pc{};

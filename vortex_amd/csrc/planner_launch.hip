@@ -156,17 +156,25 @@ static vxg_status launch_plan_k1_jobs(std::vector<K1Job>& jobs, const std::vecto
     return launch_k1g_jobs(gen, gen_runs, fuse, err, s, dt);
 }
 
-// Validate one BitPacked buffer (bitpacking/mod.rs:54-130) and describe its K1 decode.
-vxg_status make_k1_job(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
-                       Epi epi, int vw, const UnpackArgs& a, void* out, K1Job& j) {
+// Validate one BitPacked buffer (bitpacking/mod.rs:54-130).
+vxg_status check_bitpacked(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
+                           bool aligned, uint64_t* nblk) {
     if (offset > 1023) return set_error(VXG_ERR_INVALID_ARGUMENT, "Offset must be less than full block, i.e. 1024");
     if (W > unsigned(T)) return set_error(VXG_ERR_INVALID_ARGUMENT, "Unsupported bit width");
-    const uint64_t nblk = (len + offset + 1023) / 1024;
-    if (W > 0 && packed_bytes != nblk * 128ull * W)  // bitpacking/mod.rs:80-88
-        return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(nblk * 128ull * W) +
+    *nblk = (len + offset + 1023) / 1024;
+    if (W > 0 && packed_bytes != *nblk * 128ull * W)  // bitpacking/mod.rs:80-88
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "Expected " + std::to_string(*nblk * 128ull * W) +
                                                        " packed bytes, got " + std::to_string(packed_bytes));
-    if (W > 0 && (reinterpret_cast<uintptr_t>(packed) & 15))
+    if (aligned && W > 0 && (reinterpret_cast<uintptr_t>(packed) & 15))
         return set_error(VXG_ERR_INVALID_ARGUMENT, "packed buffer must be 16-byte aligned");
+    return VXG_OK;
+}
+
+// Validate one BitPacked buffer and describe its K1 decode.
+vxg_status make_k1_job(int T, unsigned W, unsigned offset, uint64_t len, const void* packed, uint64_t packed_bytes,
+                       Epi epi, int vw, const UnpackArgs& a, void* out, K1Job& j) {
+    uint64_t nblk;
+    VXG_TRY(check_bitpacked(T, W, offset, len, packed, packed_bytes, true, &nblk));
     const int ow = k1_out_width(T, epi, vw);
     if (ow != 1 && ow != 2 && ow != 4 && ow != 8 && ow != 16)  // (a Dict value width of 0 would divide by zero below)
         return set_error(VXG_ERR_INVALID_ARGUMENT, "value width must be 1, 2, 4, 8 or 16");

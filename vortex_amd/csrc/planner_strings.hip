@@ -340,4 +340,114 @@ vxg_status Planner::string_canonical(const vxg_array& a, vxg_canonical& out) {
                         static_cast<const uint8_t*>(out.validity), nullptr);
 }
 
+vxg_status Planner::string_canonical_temp(const vxg_array& s, vxg_canonical& src, std::vector<vxg_data_buffer>& lay) {
+    src = vxg_canonical{};
+    uint64_t extent;
+    VXG_TRY(string_layout(s, lay, extent));
+    const vxg_array* vnode;
+    int vkind;
+    VXG_TRY(validity_source(s, &vnode, &vkind));
+    if (vkind != 0) VXG_TRY(temp(((s.len + 31) / 32) * 4, &src.validity));
+    VXG_TRY(temp(16 * s.len, &src.views));
+    VXG_TRY(temp(extent + 16, &src.data));
+    src.data_bytes = extent;
+    src.data_buffers = lay.data();
+    src.n_data_buffers = src.data_buffers_cap = uint32_t(lay.size());
+    return string_canonical(s, src);
+}
+
+// ---- string arrays read where they lie (take_str.hip, compare_str.hip) ----------------------
+vxg_status Planner::string_bytes(const vxg_array& b, const void** p) {
+    if (b.dtype != VXG_DTYPE_PRIMITIVE || width(b) != 1)
+        return set_error(VXG_ERR_MISMATCHED_TYPES, "string bytes must be a u8 array");
+    return view_primitive(b, p);
+}
+
+vxg_status Planner::read_varbin(const vxg_array& s, VarBinSrc& v) {
+    const vxg_array* offs = child(s, 0);
+    const vxg_array* bytes = child(s, 1);
+    if (!offs || !bytes) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinArray needs offsets and bytes");
+    if (!ptype_is_int(offs->ptype) || offs->dtype != VXG_DTYPE_PRIMITIVE)
+        return set_error(VXG_ERR_MISMATCHED_TYPES, "VarBin offsets must be integers");
+    if (offs->len < s.len + 1) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets shorter than len + 1");
+    const void* pb;
+    VXG_TRY(string_bytes(*bytes, &pb));
+    IntCol oc;
+    VXG_TRY(int_column(*offs, oc));
+    if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBin offsets must be aligned to their width");
+    v = VarBinSrc{static_cast<const uint8_t*>(pb), bytes->len, to_ccol(oc)};
+    return VXG_OK;
+}
+
+vxg_status Planner::read_varbinview(const vxg_array& s, ViewSrc& v) {
+    const vxg_array* vw = child(s, 0);
+    const uint32_t nb = s.meta.varbinview.n_buffers;
+    if (!vw || s.n_children < 1 + nb)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinViewArray: missing views/data buffers");
+    const void* pv;
+    VXG_TRY(string_bytes(*vw, &pv));
+    if (vw->len < 16 * s.len) return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views shorter than 16 * len");
+    if (reinterpret_cast<uintptr_t>(pv) & 15)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "VarBinView views must be 16-byte aligned");
+    v.views = static_cast<const uint8_t*>(pv);
+    v.bufs.resize(nb);
+    for (uint32_t b = 0; b < nb; b++) {
+        const void* pb;
+        VXG_TRY(string_bytes(s.children[1 + b], &pb));
+        v.bufs[b] = StrBuf{static_cast<const uint8_t*>(pb), s.children[1 + b].len};
+    }
+    return VXG_OK;
+}
+
+vxg_status Planner::read_fsst(const vxg_array& s, FsstSrc& f) {
+    const vxg_array* sym = child(s, 0);
+    const vxg_array* slen = child(s, 1);
+    const vxg_array* codes = child(s, 2);
+    const vxg_array* ulen = child(s, 3);
+    if (!sym || !slen || !codes || !ulen || codes->encoding != VXG_ENC_VARBIN || !child(*codes, 0) || !child(*codes, 1))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "FSSTArray needs symbols, lengths, VarBin codes, lengths");
+    if (sym->len > 255 || slen->len < sym->len || width(*sym) != 8 || width(*slen) != 1)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbol table must hold at most 255 u64 symbols and their u8 lengths");
+    if (codes->len != s.len || ulen->len < s.len || child(*codes, 0)->len < s.len + 1)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST codes / lengths do not cover the array");
+    if (!ptype_is_int(child(*codes, 0)->ptype) || !ptype_is_int(ulen->ptype))
+        return set_error(VXG_ERR_MISMATCHED_TYPES, "FSST offsets and lengths must be integers");
+    const void *psym, *pslen, *pcb;
+    VXG_TRY(view_primitive(*sym, &psym));
+    VXG_TRY(view_primitive(*slen, &pslen));
+    VXG_TRY(string_bytes(*child(*codes, 1), &pcb));
+    if (reinterpret_cast<uintptr_t>(psym) & 7) return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST symbols must be 8-byte aligned");
+    IntCol oc, lc;
+    VXG_TRY(int_column(*child(*codes, 0), oc));
+    VXG_TRY(int_column(*ulen, lc));
+    if (reinterpret_cast<uintptr_t>(oc.p) % uint64_t(oc.packed ? 16 : oc.width) ||
+        reinterpret_cast<uintptr_t>(lc.p) % uint64_t(lc.packed ? 16 : lc.width))
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "FSST offsets / lengths must be aligned to their width");
+    f = FsstSrc{static_cast<const uint64_t*>(psym), static_cast<const uint8_t*>(pslen), static_cast<const uint8_t*>(pcb),
+                child(*codes, 1)->len, to_ccol(oc), to_ccol(lc), uint32_t(sym->len)};
+    return VXG_OK;
+}
+
+// ---- the one new heap of a string take / filter ----------------------------------------------
+vxg_status Planner::size_string_heap(vxg_canonical& out, uint64_t heap, const char* op, const char* rows) {
+    const std::string r(rows);
+    if (heap > 0xFFFFFFFFull) return set_error(VXG_ERR_INVALID_ARGUMENT, r + " string heap exceeds u32 view offsets");
+    if (out.data && out.data_bytes < heap)
+        return set_error(VXG_ERR_INVALID_ARGUMENT, "caller-provided data holds " + std::to_string(out.data_bytes) +
+                                                       " bytes, the " + r + " heap needs " + std::to_string(heap));
+    if (!out.data) VXG_TRY(hip_check(hipMalloc(&out.data, heap + 16), (std::string(op) + " heap alloc").c_str()));
+    out.data_bytes = heap;
+    out.n_data_buffers = 1;
+    if (out.data_buffers && out.data_buffers_cap >= 1) out.data_buffers[0] = vxg_data_buffer{0, heap};
+    return VXG_OK;
+}
+
+vxg_status Planner::read_u64(const uint64_t* dev, const char* what, uint64_t* v) {
+    const hipError_t rb = hipMemcpyAsync(v, dev, 8, hipMemcpyDeviceToHost, s_);
+    const hipError_t sync = hipStreamSynchronize(s_);  // (also after a failed copy: nothing is left in flight)
+    if (sync != hipSuccess) return hip_check(sync, (std::string(what) + " sync").c_str());
+    return rb == hipSuccess ? VXG_OK : hip_check(rb, (std::string(what) + " readback").c_str());
+}
+
 }  // namespace vxg
