@@ -13,114 +13,17 @@ import vortex_amd as V
 import vortex_amd._lib as L
 import vortex_amd.arrays as A
 import vortex_amd.encode as E
+from filter_batch_run import _guarded, mask_tensor, run  # the call and its comparison with filter_canon
 from oracle_tree import bad_bitpacked, filter_canon, slice_bitpacked
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 CANON = L.FILTB_CANONICALIZE
 
 
 def _dev():
     import torch
     return torch.device("cuda", 0)
-
-
-def mask_tensor(mask: np.ndarray, dirty_tail: bool = False):
-    """The device bitmap of a bool mask: whole u64 words, the bits past len zero (or all set)."""
-    import torch
-    n = mask.size
-    nb = ((n + 63) // 64) * 8
-    bits = np.zeros(nb * 8, dtype=bool)
-    bits[:n] = mask
-    if dirty_tail:
-        bits[n:] = True
-    host = np.packbits(bits, bitorder="little") if nb else np.zeros(0, np.uint8)
-    return torch.from_numpy(np.concatenate([host, np.zeros(8, np.uint8)])).to(_dev())  # (never an empty tensor)
-
-
-def _kind(tree):
-    return {A.DTYPE["PRIMITIVE"]: "primitive", A.DTYPE["BOOL"]: "bool"}.get(tree.dtype, "varbinview")
-
-
-def _guarded(nbytes: int):
-    import torch
-    return torch.full((nbytes + GUARD,), 0xFF, dtype=torch.uint8, device=_dev())
-
-
-def run(ctx, trees, mask: np.ndarray, flags: int = 0, dirty_tail: bool = False, want=None):
-    """vxg_filter_batch of `trees` under `mask` into exactly-sized guarded buffers; every out is
-    compared with filter_canon.  Returns the info counters."""
-    n, k = mask.size, int(mask.sum())
-    pred = A.bool_array(mask)
-    want = want if want is not None else [filter_canon(t, pred) for t in trees]
-    keep: list = []
-    nodes = [A.flatten(t.to(_dev()), keep) for t in trees]
-    cols = (C.POINTER(L.VxgArray) * len(trees))(*[C.pointer(nd) for nd in nodes])
-    outs = (L.VxgCanonical * len(trees))()
-    mt = mask_tensor(mask, dirty_tail)
-    vbytes = ((k + 31) // 32) * 4
-    bufs = []
-    for i, t in enumerate(trees):
-        kind = _kind(t)
-        b = {}
-        if kind == "primitive":
-            b["values"] = (_guarded(k * A.ptype_width(t.ptype)), k * A.ptype_width(t.ptype))
-            outs[i].values = b["values"][0].data_ptr()
-        elif kind == "bool":
-            b["values"] = (_guarded(vbytes), vbytes)
-            outs[i].values = b["values"][0].data_ptr()
-        else:
-            heap = len(want[i][0][1])
-            b["views"] = (_guarded(16 * k), 16 * k)
-            b["data"] = (_guarded(heap), heap)
-            outs[i].views, outs[i].data, outs[i].data_bytes = b["views"][0].data_ptr(), b["data"][0].data_ptr(), heap
-            table = (L.VxgDataBuffer * 1)()
-            keep.append(table)
-            outs[i].data_buffers, outs[i].data_buffers_cap = table, 1
-        if t.nullable:
-            b["validity"] = (_guarded(vbytes), vbytes)
-            outs[i].validity = b["validity"][0].data_ptr()
-        bufs.append(b)
-    kk = C.c_uint64(1 << 60)
-    info = L.VxgFilterBatchInfo()
-    L.check(ctx.lib.vxg_filter_batch(ctx.handle, cols, len(trees), C.c_void_p(mt.data_ptr()) if n else None, n, flags,
-                                     outs, C.byref(kk), C.byref(info), ctx.stream_ptr()))
-    ctx.sync()
-    assert kk.value == k, (kk.value, k)
-    for i, t in enumerate(trees):
-        (wvals, wvalid), o, b = want[i], outs[i], bufs[i]
-        what = (i, t.encoding, n, k, flags)
-        host = {name: buf.cpu().numpy() for name, (buf, _) in b.items()}
-        for name, (_, nbytes) in b.items():
-            assert (host[name][nbytes:] == 0xFF).all(), ("guard bytes written", name) + what
-        assert o.len == k and o.dtype == t.dtype, what
-        kind = _kind(t)
-        if kind == "primitive":
-            assert o.kind == V.ENC["PRIMITIVE"] and o.values_bytes == b["values"][1], what
-            assert host["values"][: b["values"][1]].tobytes() == wvals.tobytes(), what
-        elif kind == "bool":
-            assert o.kind == V.ENC["BOOL"], what
-            if k:  # (k == 0: nothing is launched, so nothing zeroes the buffers)
-                wbits = np.zeros(vbytes * 8, bool)
-                wbits[:k] = wvals
-                assert host["values"][:vbytes].tobytes() == np.packbits(wbits, bitorder="little").tobytes(), what
-        else:
-            wv, wh = wvals
-            assert o.kind == V.ENC["VARBINVIEW"] and o.data_bytes == len(wh) and o.n_data_buffers == 1, what
-            assert host["views"][: 16 * k].tobytes() == wv.tobytes(), what
-            assert host["data"][: len(wh)].tobytes() == wh.tobytes(), what
-            assert (int(o.data_buffers[0].offset), int(o.data_buffers[0].len)) == (0, len(wh)), what
-        if wvalid is None:
-            assert not o.validity, what
-        elif k:
-            assert o.validity == b["validity"][0].data_ptr(), what
-            wbits = np.zeros(vbytes * 8, bool)
-            wbits[:k] = wvalid
-            assert host["validity"][:vbytes].tobytes() == np.packbits(wbits, bitorder="little").tobytes(), what
-    res = {f: int(getattr(info, f)) for f, _ in info._fields_}
-    assert res["columns"] == len(trees) and res["mask_scans"] == (1 if n else 0), res
-    return res
 
 
 def masks_for(n: int, rng):

@@ -62,6 +62,18 @@ def test_build_is_deterministic(seed):
     assert repr(a.scalars) == repr(b.scalars) and repr(a.range) == repr(b.range)
 
 
+def test_generator_has_not_drifted():
+    """tests/golden/tree_digests.json: a sha256 per seed over `describe`, every buffer of the tree and the
+    compute inputs, recorded before Gen was extended for tests/batch_cases.py.  A seed that builds other
+    bytes changes what the GPU suite covers: add seeds, do not change what the existing ones build."""
+    import json
+    from pathlib import Path
+    want = json.loads((Path(__file__).parent / "golden" / "tree_digests.json").read_text())
+    assert sorted(want) == sorted(str(s) for s in TC.SEEDS)
+    drifted = [s for s in TC.SEEDS if TC.digest(TC.build.__wrapped__(s)) != want[str(s)]]
+    assert not drifted, f"seeds {drifted} no longer build the recorded bytes"
+
+
 @pytest.mark.parametrize("seed", TC.SEEDS)
 def test_oracle_canonical_is_the_truth(seed):
     case = TC.build(seed)

@@ -58,6 +58,10 @@ ROOTS = ([(e, "prim") for e in PRIM_ENCS] + [(e, "bool") for e in BOOL_ENCS[:4]]
         [("CHUNKED", "str")] * 4
 assert len(ROOTS) == 72
 
+# the packed shapes (vxg_compare_scalar's and vxg_filter_batch's packed route) and where chunks are cut
+PACKED_EPILOGUES = ["bp", "for", "for-shift", "zz", "zz-for", "alp-for"]
+CUT_EDGES = [1, 63, 64, 65, 1023, 1024, 1025, 4095, 4096, 4097]
+
 
 @dataclass
 class TreeCase:
@@ -751,6 +755,142 @@ class Gen:
                 sc.append(v.dtype.type(int(s[0]) - 1))
         return sc, (ops[0], s[live.size // 4], ops[1], s[(3 * live.size) // 4])
 
+    # -- columns composed by route, for the seeded batches of tests/batch_cases.py
+    @staticmethod
+    def packed_epilogues(pt: str) -> list:
+        """The packed shapes a chunk of ptype `pt` can have (PACKED_EPILOGUES)."""
+        if pt in FLOATS:
+            return ["alp-for"]
+        return ["bp", "for", "for-shift"] if pt in UNSIGNED else ["for", "for-shift", "zz", "zz-for"]
+
+    def cut_lens(self, n: int, k: int) -> list:
+        """k chunk lengths that sum to n: cuts biased to the word, block and tile edges, zero-length
+        and one-row chunks among them."""
+        edges = [e for e in CUT_EDGES if e <= n] or [0]
+        cuts = []
+        for _ in range(k - 1):
+            if cuts and self.chance(0.25):  # a zero-length or a one-row chunk
+                c = cuts[int(self.rng.integers(0, len(cuts)))] + int(self.pick([0, 1]))
+            elif self.chance(0.6):
+                c = int(self.pick(edges)) + int(self.pick([0, 0, 1024, 4096]))
+            else:
+                c = int(self.rng.integers(0, n + 1))
+            cuts.append(min(c, n))
+        cuts = [0] + sorted(cuts) + [n]
+        return [b - a for a, b in zip(cuts, cuts[1:])]
+
+    def packed_leaf(self, u: np.ndarray, W: int, start: int, n: int, varg) -> Array:
+        """Rows [start, start + n) of `u` (unsigned, values wider than W bits become patches) as a
+        BitPacked array of width W with the validity `varg`: a slice when start > 0 or rows follow."""
+        bp = E.encode_bitpacked(u, bit_width=W)
+        patches = None
+        if bp.meta["has_patches"]:
+            idx = np.flatnonzero(u >> u.dtype.type(W)).astype(np.uint64)
+            patches = A.sparse(self.index_array(idx), bp.children[0].children[1], u.size)
+        node = A.bitpacked(bp.buffers[0], bp.ptype, W, u.size, 0, patches)
+        if (start, n) != (0, u.size):
+            node = slice_any(node, start, start + n)
+        return A.bitpacked(node.buffers[0], node.ptype, W, n, node.meta["offset"],
+                           node.children[0] if node.meta["has_patches"] else None, validity=varg)
+
+    def packed_chunk(self, pt: str, n: int, epilogue: str, patched: bool, vkind: str = "NON_NULLABLE",
+                     sliced: bool = False):
+        """n >= 1 rows of ptype `pt` in the packed shape `epilogue`, its BitPacked leaf of a drawn bit
+        width with or without patches (an ALP chunk: and / or exceptions), with the leaf's validity of
+        kind `vkind`, a slice of a longer array when `sliced` -> (node, values, valid mask | None)."""
+        r = self.rng
+        T = 8 * A.ptype_width(pt)
+        start, total = self.slice_window(n) if sliced else (0, n)
+        varg, m = self.validity(n, [vkind])
+        rows = start + np.unique(np.concatenate([r.choice(n, max(n // 40, 1), replace=False),
+                                                 [0] if self.chance(0.5) else [], [n - 1] if self.chance(0.5) else []])
+                                 ).astype(np.int64)  # patched rows: the first and the last row among them, or not
+        if total > n and self.chance(0.7):  # ... and one outside the slice
+            rows = np.append(rows, start - 1)
+        if epilogue == "alp-for":
+            dt = NP_OF_PTYPE[pt]
+            digits = int(self.pick([0, 1] if pt == "f32" else [1, 2, 4]))
+            vals = np.round(r.uniform(-1000, 1000, total), digits).astype(dt) + dt(0)  # (no -0.0: ALP gives +0.0)
+            wide, exc = (patched and self.chance(0.7)), (patched and self.chance(0.6))
+            if patched and not (wide or exc):
+                wide = True
+            if wide:  # decimals of more digits: values the leaf's width does not hold
+                vals[rows] = np.round(r.uniform(1.5e5, 2e5, rows.size), digits).astype(dt)
+            if exc:   # what ALP cannot encode
+                at = rows[:: 2] if wide and rows.size > 1 else rows
+                vals[at] = (r.standard_normal(at.size) * np.pi * 1e3).astype(dt)
+            e, f, enc, idx, pv = E.alp_encode(vals)
+            sp = None
+            if idx.size:
+                sp = slice_any(A.sparse(self.index_array(idx), A.primitive(pv, validity="ALL_VALID"), total),
+                               start, start + n)
+                sp = sp if sp.children[0].len else None
+            u, ref, shift = self.for_parts(enc)
+            base = np.delete(u, rows) if wide and rows.size < total else u
+            W = max(int(base.max(initial=0)).bit_length(), 1)
+            if W >= T:
+                W = T - 1
+            leaf = self.packed_leaf(u, W, start, n, varg)
+            node = A.alp(A.frame_of_reference(leaf, ref, shift, A.PTYPE_OF_NP[enc.dtype]), e, f, sp)
+            return node, vals[start: start + n].copy(), m
+        upt = A.unsigned_of(pt)
+        ut = NP_OF_PTYPE[upt]
+        shift = {"for-shift": int(r.integers(1, 4)), "zz-for": int(self.pick([0, 0, 1]))}.get(epilogue, 0)
+        top = T - 1 - shift  # the patched values stay below 2^top, so that the shift loses no bit
+        W = int(r.integers(1, top)) if patched else int(r.integers(1, top + 1))
+        u = r.integers(0, 1 << W, total, dtype=np.uint64)
+        u[r.integers(0, total, 2)] = (1 << W) - 1  # the width's extremes are present
+        u[r.integers(0, total, 2)] = 0
+        if patched:
+            u[rows] = r.integers(1 << W, 1 << top, rows.size, dtype=np.uint64)
+        u = u.astype(ut)
+        leaf = self.packed_leaf(u, W, start, n, varg)
+        u = u[start: start + n]
+        info = np.iinfo(NP_OF_PTYPE[pt])
+        if epilogue == "bp":
+            return leaf, u.copy(), m
+        if epilogue in ("for", "for-shift"):  # a reference near either end of the type: the add wraps
+            ref = int(self.pick([3, info.min + 7, info.max - 20, info.max // 3])) if info.min else \
+                int(self.pick([3, info.max - 40, info.max // 3]))
+            bits = np.array([ref], NP_OF_PTYPE[pt]).view(ut)[0]
+            vals = ((u << ut(shift)) + bits).view(NP_OF_PTYPE[pt])
+            return A.frame_of_reference(leaf, ref, shift, pt), vals, m
+        if epilogue == "zz-for":  # ZigZag over FoR(BitPacked): the FoR is of the unsigned type
+            ref = int(self.pick([0, 9, int(np.iinfo(ut).max) - 40]))
+            u = (u << ut(shift)) + ut(ref)
+            leaf = A.frame_of_reference(leaf, ref, shift, upt)
+        vals = ((u >> ut(1)) ^ (ut(0) - (u & ut(1)))).view(NP_OF_PTYPE[pt])
+        return A.zigzag(leaf), vals, m
+
+    def empty_chunk(self, pt: str, packed: bool) -> Array:
+        """A zero-length chunk: a Primitive array or, for integers, an empty FoR(BitPacked)."""
+        if not packed or pt in FLOATS:
+            return A.primitive(np.zeros(0, NP_OF_PTYPE[pt]), validity=self.pick([None, None, "ALL_VALID"]))
+        leaf = E.encode_bitpacked(np.zeros(0, NP_OF_PTYPE[A.unsigned_of(pt)]), bit_width=3, allow_patches=False)
+        return A.frame_of_reference(leaf, 0, 0, pt)
+
+    def chunked_column(self, parts: list, pt: str, n: int, extra: int = 0, start: int = 0):
+        """The ChunkedArray of `parts` ((node, values, valid mask | None) each) of n + extra rows, and
+        rows [start, start + n) of it when extra > 0 -> (node, values, valid mask | None)."""
+        node = A.chunked([p[0] for p in parts])
+        vals = np.concatenate([np.zeros(0, NP_OF_PTYPE[pt])] + [p[1] for p in parts])
+        valid = None
+        if any(p[2] is not None for p in parts):
+            valid = np.concatenate([np.ones(p[0].len, bool) if p[2] is None else p[2] for p in parts])
+        assert node.len == n + extra
+        if extra:
+            node, vals = slice_any(node, start, start + n), vals[start: start + n].copy()
+            valid = None if valid is None else valid[start: start + n].copy()
+        return node, vals, valid
+
+    def sliced_primitive(self, pt: str, n: int, vkind: str):
+        """A Primitive array that is a slice of a longer one: its values do not start its buffer."""
+        start, total = self.slice_window(n)
+        vals = self.values_for("PRIMITIVE", pt, total)
+        varg, m = self.validity(total, [vkind])
+        node = slice_any(A.primitive(vals, validity=varg), start, start + n)
+        return node, vals[start: start + n].copy(), None if m is None else m[start: start + n].copy()
+
 
 @functools.lru_cache(maxsize=None)
 def build(seed: int) -> TreeCase:
@@ -771,3 +911,50 @@ def build(seed: int) -> TreeCase:
 
 
 SEEDS = list(range(72))
+
+
+# ---------------------------------------------------------------------------- digests
+def tree_bytes(a: Array, out: list) -> list:
+    """Everything a tree is made of, in walk order: each node's header, then its buffers' bytes."""
+    def plain(v):  # (numpy scalars print differently from one numpy to the next)
+        return bytes(v) if isinstance(v, (bytes, bytearray)) else v.item() if isinstance(v, np.generic) else v
+
+    out.append((int(a.encoding), int(a.len), int(a.dtype), str(a.ptype), bool(a.nullable), int(a.validity),
+                sorted((k, plain(v)) for k, v in a.meta.items())))
+    out.extend(np.ascontiguousarray(b).tobytes() for b in a.buffers)
+    for c in a.children:
+        tree_bytes(c, out)
+    return out
+
+
+def digest(case: TreeCase) -> str:
+    """sha256 over `describe`, every buffer of the tree and the compute inputs: what
+    tests/golden/tree_digests.json records per seed, so that a change of the generator is seen."""
+    import hashlib
+    h = hashlib.sha256()
+
+    def feed(x):
+        h.update(x if isinstance(x, bytes) else repr(x).encode())
+        h.update(b"\x00")
+
+    def feed_tree(a):
+        for x in tree_bytes(a, []):
+            feed(x)
+
+    feed(case.describe)
+    feed(case.kind)
+    feed_tree(case.tree)
+    for name, ix in case.take_sets:
+        feed((name, str(ix.dtype)))
+        feed(ix.tobytes())
+    for name, p in case.predicates:
+        feed(name)
+        feed_tree(p)
+    for s in list(case.scalars) + list(case.range or ()):
+        feed(s if isinstance(s, (bytes, str)) else (str(np.asarray(s).dtype), np.asarray(s).tobytes()))
+    return h.hexdigest()
+
+
+if __name__ == "__main__":  # PYTHONPATH=. python tests/tree_cases.py > tests/golden/tree_digests.json
+    import json
+    print(json.dumps({str(s): digest(build(s)) for s in SEEDS}, indent=0))
