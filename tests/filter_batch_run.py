@@ -93,13 +93,17 @@ def buffer_sizes(trees, want, k: int):
     return out
 
 
-def call(ctx, trees, mask: np.ndarray, flags: int = 0, dirty_tail: bool = False, want=None, allocate: bool = False):
+def call(ctx, trees, mask: np.ndarray, flags: int = 0, dirty_tail: bool = False, want=None, allocate: bool = False,
+         nodes=None):
     """vxg_filter_batch of `trees` under `mask` -> (k, host buffers, outs, info) with everything in
-    host memory."""
+    host memory.  `nodes`: prepared vxg_array nodes of `trees` (e.g. the file reader's, over a file's
+    bytes in device memory) that go to the engine as they stand; by default every tree is uploaded
+    and flattened here."""
     import torch
     n, k = mask.size, int(mask.sum())
     keep: list = []
-    nodes = [A.flatten(t.to(_dev()), keep) for t in trees]
+    if nodes is None:
+        nodes = [A.flatten(t.to(_dev()), keep) for t in trees]
     cols = (C.POINTER(L.VxgArray) * len(trees))(*[C.pointer(nd) for nd in nodes])
     outs = (L.VxgCanonical * len(trees))()
     mt = mask_tensor(mask, dirty_tail)
@@ -190,12 +194,12 @@ def check_outputs(host, outs, want, trees, n: int, k: int, flags: int = 0, at: s
 
 
 def run(ctx, trees, mask: np.ndarray, flags: int = 0, dirty_tail: bool = False, want=None, allocate: bool = False,
-        at: str = ""):
+        at: str = "", nodes=None):
     """vxg_filter_batch of `trees` under `mask` into exactly-sized guarded buffers; every out is
     compared with filter_canon.  Returns the info counters."""
     n, k = mask.size, int(mask.sum())
     want = want if want is not None else [filter_canon(t, A.bool_array(mask)) for t in trees]
-    kk, host, outs, res = call(ctx, trees, mask, flags, dirty_tail, want, allocate)
+    kk, host, outs, res = call(ctx, trees, mask, flags, dirty_tail, want, allocate, nodes)
     assert kk == k, (kk, k, at)
     check_outputs(host, outs, want, trees, n, k, flags, at)
     assert res["columns"] == len(trees) and res["mask_scans"] == (1 if n else 0), (res, at)

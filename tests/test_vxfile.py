@@ -9,6 +9,10 @@ must fail with InvalidSerde, never crash.  Parity of the written BYTES with the 
 unpinned (no reference-written file exists in the reference tree and it cannot be built here);
 the flexbuffer/flatbuffer decoders are checked against hand-built buffers of the published
 formats instead.
+
+The seeded round trip -- every tree of tests/tree_cases.py and every batch of tests/batch_cases.py
+written as a file and read back, per chunk range and for both typed-vector settings -- lives in
+tests/test_file_cases.py; `_check_tree` is tests/file_tree_check.check_tree, shared with it.
 """
 import ctypes as C
 import struct
@@ -20,35 +24,10 @@ import vortex_amd._lib as L
 import vortex_amd.arrays as A
 import vortex_amd.encode as E
 from tools import lineitem as LI
+from file_tree_check import check_tree as _check_tree
+from file_tree_check import leaf_buffers as _leaf_buffers
 from tools import vxfile as X
 from vortex_amd.file import VortexFile
-
-
-def _check_tree(node, a, data: np.ndarray, path="root"):
-    if a.encoding == X.ENC_EXTENSION:
-        a = a.children[0]
-    assert node.encoding == a.encoding, path
-    assert node.len == a.len, path
-    assert node.dtype == a.dtype, path
-    if a.dtype == L.DTYPE["PRIMITIVE"]:
-        assert L.PTYPES[node.ptype] == a.ptype, path
-    assert bool(node.nullable) == bool(a.nullable), path
-    assert node.validity == a.validity, path
-    m = L.VxgMeta()
-    A._fill_meta(m, a)
-    assert bytes(m) == bytes(node.meta), (path, a.encoding, a.meta)
-    if a.buffers:
-        want = np.ascontiguousarray(a.buffers[0]).view(np.uint8).reshape(-1)
-        assert node.n_buffers == 1, path
-        off, n = int(node.buffers[0].ptr or 0), int(node.buffers[0].len)
-        assert off % 64 == 0, path  # 64-byte aligned in the file (lib.rs:15)
-        assert n == want.size, path
-        assert data[off: off + n].tobytes() == want.tobytes(), path
-    else:
-        assert node.n_buffers == 0, path
-    assert node.n_children == len(a.children), path
-    for i, c in enumerate(a.children):
-        _check_tree(node.children[i], c, data, f"{path}/{i}")
 
 
 def _lineitem(rows=5000, chunk_rows=2048):
@@ -227,13 +206,6 @@ def test_region_must_cover_every_chunk():
     for k, ch in enumerate(cols[0][1]):
         _check_tree(node.children[1 + k], ch, raw)
     f.close()
-
-
-def _leaf_buffers(node):
-    out = [(int(node.buffers[i].ptr or 0), int(node.buffers[i].len)) for i in range(node.n_buffers)]
-    for i in range(node.n_children):
-        out += _leaf_buffers(node.children[i])
-    return out
 
 
 def test_flatbuffer_postscript_is_32_bytes():

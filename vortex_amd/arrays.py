@@ -476,6 +476,24 @@ def flatten(a: Array, keep: list) -> _lib.VxgArray:
     return node
 
 
+@dataclass
+class _NodeShape:
+    """What the bindings read off an input: an Array has it; a VxgArray node is given it."""
+    len: int
+    dtype: int
+    ptype: str
+    nullable: bool
+
+
+def _node_of(a, keep: list):
+    """-> (vxg_array node, shape) of an input of the compute bindings: an Array tree is flattened
+    (device buffers), an already-flattened VxgArray node -- e.g. one of the trees a vxg_file reader
+    built over a file's bytes in HBM -- goes to the engine as it stands, the way Plan takes it."""
+    if isinstance(a, _lib.VxgArray):
+        return a, _NodeShape(int(a.len), int(a.dtype), PTYPES[a.ptype], bool(a.nullable))
+    return flatten(a, keep), a
+
+
 # ---- context + canonical output ----------------------------------------------------------
 class Context:
     """One vxg_ctx per device (one context per device, thread-safe calls)."""
@@ -643,7 +661,7 @@ def take(a: Array, indices, ctx: Context, sync: bool = True, force_canonical: bo
     (VXG_TAKE_CANONICALIZE) canonicalizes the whole array first: the same bytes, for diagnostics."""
     import torch
     keep: list = []
-    node = flatten(a, keep)
+    node, a = _node_of(a, keep)
     dev = torch.device("cuda", ctx.device)
     if isinstance(indices, torch.Tensor):
         it = indices.to(dev)
@@ -714,8 +732,8 @@ def filter(a: Array, predicate: Array, ctx: Context) -> Canonical:
     Synchronous, like the reference (the filtered length is read back)."""
     import torch
     keep: list = []
-    node = flatten(a, keep)
-    pnode = flatten(predicate, keep)
+    node, a = _node_of(a, keep)
+    pnode, _ = _node_of(predicate, keep)
     dev = torch.device("cuda", ctx.device)
     n = a.len
     out = _lib.VxgCanonical()
@@ -777,7 +795,7 @@ def compare(a: Array, op: str, scalar, ctx: Context, null_as_false: bool = False
     if op not in _lib.CMP_OP:
         raise VortexError(3, f"compare: unknown operator {op!r}")
     keep: list = []
-    node = flatten(a, keep)
+    node, a = _node_of(a, keep)
     dev = torch.device("cuda", ctx.device)
     nbytes = ((a.len + 63) // 64) * 8
     vals = out_values if out_values is not None else torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
@@ -818,7 +836,9 @@ def row_filter(preds, ctx: Context, flags: int = 0, sync: bool = True, out_value
     op as in `compare`, scalar a number for a primitive column, bytes or str for a utf8/binary one.
     The result is a non-nullable Bool canonical whose bit i is set where every conjunct is true and
     its column is valid in row i, so `predicate_from(res)` is a filter predicate as it stands.
-    Each distinct Array OBJECT is flattened once: conjuncts on the same object share one node, and a
+    Each distinct Array OBJECT is flattened once (an already-flattened VxgArray node, e.g. a file
+    reader's, is passed as it stands and told apart by its address): conjuncts on the same object
+    share one node, and a
     lower and an upper bound on one node are evaluated as one two-sided compare (`flags`:
     0 = the engine's choice, _lib.ROWF_FUSE_RANGES, _lib.ROWF_NO_FUSE_RANGES; the bytes never
     differ).  `res.info` holds vxg_row_filter_info's counters.  count: True = the true count is taken
@@ -835,11 +855,12 @@ def row_filter(preds, ctx: Context, flags: int = 0, sync: bool = True, out_value
     for i, (a, op, scalar) in enumerate(preds):
         if op not in _lib.CMP_OP:
             raise VortexError(3, f"row_filter: unknown operator {op!r}")
-        if id(a) not in nodes:
-            node = flatten(a, keep)
-            keep.append(node)
-            nodes[id(a)] = node
-        arr[i].column = C.pointer(nodes[id(a)])
+        key = C.addressof(a) if isinstance(a, _lib.VxgArray) else id(a)  # (a node: its struct)
+        if key not in nodes:
+            nodes[key] = _node_of(a, keep)
+            keep.append(nodes[key])
+        node, a = nodes[key]
+        arr[i].column = C.pointer(node)
         arr[i].op = _lib.CMP_OP[op]
         if a.dtype in (DTYPE["UTF8"], DTYPE["BINARY"]):
             sc = scalar.encode("utf-8") if isinstance(scalar, str) else bytes(scalar)
@@ -849,7 +870,7 @@ def row_filter(preds, ctx: Context, flags: int = 0, sync: bool = True, out_value
         sbuf = (C.c_uint8 * max(len(sc), 8)).from_buffer_copy(sc.ljust(8, b"\0"))
         keep.append(sbuf)
         arr[i].scalar_host = C.cast(sbuf, C.c_void_p)
-    n = preds[0][0].len
+    n = int(preds[0][0].len)
     dev = torch.device("cuda", ctx.device)
     nbytes = ((n + 63) // 64) * 8
     vals = out_values if out_values is not None else torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
@@ -901,7 +922,7 @@ def filter_batch(columns, mask, ctx: Context, flags: int = 0, sync: bool = True,
         n, mt, k_hint = int(length), mask, None
     dev = torch.device("cuda", ctx.device)
     keep: list = []
-    nodes = [flatten(a, keep) for a in columns]
+    nodes, columns = zip(*[_node_of(a, keep) for a in columns]) if columns else ((), ())
     cols = (C.POINTER(_lib.VxgArray) * max(len(columns), 1))(*[C.pointer(nd) for nd in nodes])
     outs = (_lib.VxgCanonical * max(len(columns), 1))()
     cap = n if k_hint is None else int(k_hint)  # rows every output has room for
