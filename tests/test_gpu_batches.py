@@ -20,7 +20,7 @@ import vortex_amd._lib as L
 import vortex_amd.arrays as A
 from filter_batch_run import mask_tensor, run
 from oracle_tree import filter_canon
-from test_gpu_trees import check_rows
+from test_gpu_trees import check_rows, picked
 from vortex_amd._lib import ENC
 
 pytestmark = pytest.mark.gpu
@@ -118,12 +118,15 @@ def check_info(info, cols, n, k, at, forced=False):
     assert info["packed_launches"] >= len(by["packed"]), (info, by, at)
 
 
-@pytest.mark.parametrize("seed", SEEDS, ids=IDS)
-def test_filter_batch(ctx, seed):
-    st = staged(seed)
+# The routes as callables of (ctx, st): the tests below run them on the default stream with every
+# input of the batch; tests/test_gpu_streams.py runs them on a caller's stream with a selection.
+def filter_batch(ctx, st, masks=None):
+    """`masks`: names of the masks to run."""
     n = st.case.n
     conj_masks = [name for name, _, _ in st.case.masks if name.startswith("conjunction-")]
     for name, mask, dirty in st.case.masks:
+        if not picked(masks, name):
+            continue
         k = int(mask.sum())
         want = st.want(name, mask)
         at = st.at(f"mask {name}, k={k}")
@@ -142,11 +145,17 @@ def test_filter_batch(ctx, seed):
 
 
 @pytest.mark.parametrize("seed", SEEDS, ids=IDS)
-def test_row_filter_then_filter_batch(ctx, seed):
-    st = staged(seed)
+def test_filter_batch(ctx, seed):
+    filter_batch(ctx, staged(seed))
+
+
+def row_filter_then_filter_batch(ctx, st, conjunctions=None):
+    """`conjunctions`: names of the conjunctions to run."""
     n = st.case.n
     nb = ((n + 63) // 64) * 8
     for name, conj, mask in st.case.conjunctions:
+        if not picked(conjunctions, name):
+            continue
         want_bits, wmask, count = row_filter_expected.expected([(st.trees[i], op, s) for i, op, s in conj])
         assert np.array_equal(wmask, mask)
         kept = st.want("conjunction-" + name, mask)
@@ -169,6 +178,11 @@ def test_row_filter_then_filter_batch(ctx, seed):
             check_info(binfo, st.cols, n, k, at + ", then filter_batch")
             for c, got, (wvals, wvalid) in zip(st.cols, outs, kept):
                 check_rows(c.kind, got, wvals, wvalid, at + f", then filter_batch: {c.describe}")
+
+
+@pytest.mark.parametrize("seed", SEEDS, ids=IDS)
+def test_row_filter_then_filter_batch(ctx, seed):
+    row_filter_then_filter_batch(ctx, staged(seed))
 
 
 @pytest.mark.parametrize("seed", SEEDS, ids=IDS)

@@ -72,9 +72,14 @@ def staged(seed) -> Staged:
 
 
 # ---------------------------------------------------------------------------- canonicalize
-@pytest.mark.parametrize("seed", TC.SEEDS)
-def test_direct_and_plan(ctx, seed):
-    st = staged(seed)
+def picked(selection, name) -> bool:
+    """`name` is among the inputs a route was asked to run (None: every input of the case)."""
+    return selection is None or name in selection
+
+
+# The routes as callables of (ctx, st): the tests below run them on the default stream with every
+# input of the case; tests/test_gpu_streams.py runs them on a caller's stream with a selection.
+def direct_and_plan(ctx, st):
     kind = st.case.kind
     direct = A.canonicalize(st.dev, ctx)
     check_rows(kind, direct, st.want, st.valid, st.at("direct"))
@@ -88,12 +93,12 @@ def test_direct_and_plan(ctx, seed):
     check_rows(kind, direct, st.want, st.valid, st.at("direct, after the plan"))
 
 
-@pytest.mark.parametrize("fuse", ["1", "0"])
-@pytest.mark.parametrize("batch", ["1", "0"])
-@pytest.mark.parametrize("group", range(len(GROUPS)))
-def test_plan_over_eight_trees(ctx, group, batch, fuse):
-    """One plan over eight trees: every output checked on two launches, and the direct outputs taken
-    before it checked again afterwards (a plan that writes outside its own outputs is seen)."""
+@pytest.mark.parametrize("seed", TC.SEEDS)
+def test_direct_and_plan(ctx, seed):
+    direct_and_plan(ctx, staged(seed))
+
+
+def plan_over_eight_trees(ctx, group, batch, fuse):
     sts = [staged(s) for s in GROUPS[group]]
     direct = [A.canonicalize(st.dev, ctx) for st in sts]
     with env_set(VXG_PLAN_FUSE=fuse), plan_mode(batch):
@@ -110,11 +115,21 @@ def test_plan_over_eight_trees(ctx, group, batch, fuse):
         check_rows(st.case.kind, d, st.want, st.valid, st.at(f"direct, after the plan of seeds {GROUPS[group]}"))
 
 
+@pytest.mark.parametrize("fuse", ["1", "0"])
+@pytest.mark.parametrize("batch", ["1", "0"])
+@pytest.mark.parametrize("group", range(len(GROUPS)))
+def test_plan_over_eight_trees(ctx, group, batch, fuse):
+    """One plan over eight trees: every output checked on two launches, and the direct outputs taken
+    before it checked again afterwards (a plan that writes outside its own outputs is seen)."""
+    plan_over_eight_trees(ctx, group, batch, fuse)
+
+
 # ---------------------------------------------------------------------------- take
-@pytest.mark.parametrize("seed", TC.SEEDS)
-def test_take(ctx, seed):
-    st = staged(seed)
+def take(ctx, st, sets=None):
+    """`sets`: names of the take sets to run."""
     for name, idx in st.case.take_sets:
+        if not picked(sets, name):
+            continue
         want, wvalid = take_canon(st.tree, idx, canonical=(st.want, st.valid) if st.case.kind == "str" else None)
         for force in (False, True):
             res = A.take(st.dev, idx, ctx, force_canonical=force)
@@ -122,14 +137,25 @@ def test_take(ctx, seed):
                        st.at(f"take {name}: {idx.size} x {idx.dtype} force_canonical={force}"))
 
 
-# ---------------------------------------------------------------------------- filter
 @pytest.mark.parametrize("seed", TC.SEEDS)
-def test_filter(ctx, seed):
-    st = staged(seed)
+def test_take(ctx, seed):
+    take(ctx, staged(seed))
+
+
+# ---------------------------------------------------------------------------- filter
+def filter_rows(ctx, st, predicates=None):
+    """`predicates`: names of the predicates to run."""
     for name, pred in st.case.predicates:
+        if not picked(predicates, name):
+            continue
         want, wvalid = filter_canon(st.tree, pred)
         res = A.filter(st.dev, pred.to(_dev()), ctx)
         check_rows(st.case.kind, res, want, wvalid, st.at(f"filter {name}"))
+
+
+@pytest.mark.parametrize("seed", TC.SEEDS)
+def test_filter(ctx, seed):
+    filter_rows(ctx, staged(seed))
 
 
 # ---------------------------------------------------------------------------- compare
@@ -141,13 +167,16 @@ def compare_want(st, op, scalar):
     return compare_expected.bitmap(m), (None if st.valid is None else compare_expected.bitmap(st.valid)), m
 
 
-@pytest.mark.parametrize("seed", VALUE_SEEDS)
-def test_compare(ctx, seed):
-    st = staged(seed)
+def compare(ctx, st, scalars=None, ops=None):
+    """`scalars`: positions in the case's list of scalars to run; `ops`: the operators."""
     n = st.tree.len
     nb = ((n + 63) // 64) * 8
-    for scalar in st.case.scalars:
+    for i, scalar in enumerate(st.case.scalars):
+        if not picked(scalars, i):
+            continue
         for op in OPS:
+            if not picked(ops, op):
+                continue
             want, want_valid, _ = compare_want(st, op, scalar)
             for null_as_false in (False, True):
                 at = st.at(f"compare {op} {scalar!r} null_as_false={null_as_false}")
@@ -161,10 +190,13 @@ def test_compare(ctx, seed):
                         "validity differs, " + at
 
 
-# ---------------------------------------------------------------------------- row filter
 @pytest.mark.parametrize("seed", VALUE_SEEDS)
-def test_row_filter(ctx, seed):
-    st = staged(seed)
+def test_compare(ctx, seed):
+    compare(ctx, staged(seed))
+
+
+# ---------------------------------------------------------------------------- row filter
+def row_filter(ctx, st):
     lo_op, lo, hi_op, hi = st.case.range
     want, mask, count = row_filter_expected.expected([(st.tree, lo_op, lo), (st.tree, hi_op, hi)])
     nb = ((st.tree.len + 63) // 64) * 8
@@ -176,3 +208,8 @@ def test_row_filter(ctx, seed):
         assert res.true_count == count, f"true count {res.true_count} != {count}, " + at
         got = A.filter(st.dev, A.predicate_from(res), ctx)
         check_rows(st.case.kind, got, kept, kvalid, at + ", then filter")
+
+
+@pytest.mark.parametrize("seed", VALUE_SEEDS)
+def test_row_filter(ctx, seed):
+    row_filter(ctx, staged(seed))

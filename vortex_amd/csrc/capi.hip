@@ -238,6 +238,7 @@ vxg_status vxg_canonical_size(vxg_ctx* ctx, const vxg_array* a, uint64_t* values
     VXG_TRY(use_device(ctx));
     if (!a) return set_error(VXG_ERR_INVALID_ARGUMENT, "null array");
     Planner p(ctx, nullptr);
+    p.as_query();
     uint64_t vb = 0, db = 0;
     VXG_TRY(p.canonical_size(*a, vb, db));
     if (values_bytes) *values_bytes = vb;
@@ -250,6 +251,7 @@ vxg_status vxg_canonical_layout(vxg_ctx* ctx, const vxg_array* a, uint64_t* valu
     VXG_TRY(use_device(ctx));
     if (!a) return set_error(VXG_ERR_INVALID_ARGUMENT, "null array");
     Planner p(ctx, nullptr);
+    p.as_query();
     uint64_t vb = 0, db = 0;
     uint32_t n = 0;
     if (is_string(*a)) {

@@ -147,6 +147,10 @@ class Planner {
     vxg_status row_filter(const vxg_predicate* preds, uint32_t n_preds, uint32_t flags, vxg_canonical& out,
                           uint64_t* count_dev, vxg_row_filter_info& info);
     vxg_status canonical_size(const vxg_array& a, uint64_t& vb, uint64_t& db);
+    // A size / layout query (vxg_canonical_size, vxg_canonical_layout): it is handed no stream, so
+    // where it has to read the device (string_layout's FSST sums) it first waits for the whole
+    // device -- the caller's uploads may be enqueued on any stream.
+    void as_query() { query_ = true; }
     // Data buffers of a string canonical, placed 16-byte aligned in one allocation.
     vxg_status string_layout(const vxg_array& a, std::vector<vxg_data_buffer>& bufs, uint64_t& extent);
     static vxg_status string_buffer_count(const vxg_array& a, uint32_t& n);
@@ -155,6 +159,7 @@ class Planner {
     vxg_ctx* ctx_;
     hipStream_t s_;
     std::vector<void*> temps_;
+    bool query_ = false;  // as_query()
     // Recording a plan: temporaries are plain allocations owned by the plan (alive for all its
     // replays) instead of stream-ordered ones, and chunk tables longer than a kernel argument
     // holds become device tables (one launch per kernel group).

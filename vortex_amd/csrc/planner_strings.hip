@@ -78,6 +78,10 @@ vxg_status Planner::string_layout(const vxg_array& a, std::vector<vxg_data_buffe
     std::vector<std::pair<size_t, const vxg_array*>> fsst;
     VXG_TRY(string_lens(a, lens, fsst));
     if (!fsst.empty()) {  // fsst/canonical.rs:29-42: heap size = sum of uncompressed lengths
+        // a query runs on the legacy default stream, which a non-blocking stream's uploads are not
+        // ordered with: every upload enqueued so far (any stream) lands before the sums read it
+        // (as vxg_plan_create_ex(VXG_PLAN_MEASURE) does before it runs the decode)
+        if (query_) VXG_TRY(hip_check(hipDeviceSynchronize(), "layout query: device synchronize"));
         void* d;
         VXG_TRY(temp(8 * fsst.size(), &d));
         for (size_t k = 0; k < fsst.size(); k++) {
